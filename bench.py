@@ -10,11 +10,17 @@ in HBM.  Workload = BASELINE.json configs[1]: PNA hidden 200, dep
 batch 512 per GPU, fp32.  N>1: molecules sharded by rank (weak scaling, 512 per GPU), all-gathered negatives,
 gradient all-reduce, and - the headline `value` - BatchNorm statistics over the GLOBAL batch (the reference normalises over
 every row it is given: only this mode reproduces its loss; csrc/peer.hip exchanges the statistics between the ranks' kernels);
-the step with per-rank statistics is measured right after it and reported as config.local_bn (3dinfomax_amd/dist.py).
+with --full the step with per-rank statistics is measured right after it and reported as config.local_bn (3dinfomax_amd/dist.py).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline     - the PNA aggregation kernel (K4): algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak
+A plain run sets up, runs W warm-up and K timed steps, and prints ONE JSON line (rank 0) with the contract fields (`value`,
+`ms_per_step`, the per-step device-time spread and the final loss).  --full measures everything else after the timed steps and adds
+it to the line:
+  roofline     - the PNA aggregation kernel (K4): algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak, per-family figures
   cpu_baseline - the oracle (CPU port of the reference path) timed on this host on a bounded sample (N=1 only)
+  config       - extra_workloads (the other BASELINE.json configurations), the rates with batch assembly, at N > 1 the other
+                 BatchNorm mode and the per-collective times
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: the loss, the two embeddings and
+the state of both models after the optimizer step.  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import importlib
@@ -103,6 +109,12 @@ def parse():
                          'helper thread); box-dependent: helps a host-bound loop, costs a device-bound one')
     ap.add_argument('--no-extra-workloads', action='store_true',
                     help='skip the short windows of the other BASELINE.json configs after the timed region (config.extra_workloads)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the roofline, per-family and collective figures, the batch-assembly rates, '
+                         'the other BatchNorm mode (N > 1), the other BASELINE.json configurations and the CPU baseline (the --no-* '
+                         'switches above leave parts out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0) to DIR/<name>.npy (float32, at most 64 MB in all)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launch check only: start the ranks, form the process group, count the ranks the communicator sees '
                          '(all-reduce of ones) and print the JSON line without running a model (no GPU needed with --backend gloo)')
@@ -385,6 +397,28 @@ def extra_workloads(amd, ops, dev, depth):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """np.save each of {name: array} to path/<name>.npy as float32.  Over DUMP_LIMIT_BYTES in all, every array larger than an equal
+    share of it is replaced by a fixed, seeded sample of its elements (sorted flat indices), the same on every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def model_state(module):
+    """every floating-point entry of the state dict (parameters, BatchNorm running statistics), flattened in state-dict order"""
+    return torch.cat([t.detach().reshape(-1).float() for t in module.state_dict().values() if t.is_floating_point()]).cpu().numpy()
+
+
 def dry_run(args, world, rank):
     """--dry-run: the launch path and the process group only (CPU tests; `--backend gloo` needs no GPU)."""
     import torch.distributed as dist
@@ -492,13 +526,14 @@ def main():
     def step(i):
         g2, g3, _ = batches[i % pool]
         a, b = g2.local_copy(), g3.local_copy()
-        loss = loss_fn(pna(a), net(b), nodes_per_graph=a.batch_num_nodes())
+        z2, z3 = pna(a), net(b)
+        loss = loss_fn(z2, z3, nodes_per_graph=a.batch_num_nodes())
         loss.backward()
         if use_dist:
             adist.allreduce_grads(params)
         optim.step()
         optim.zero_grad()
-        return loss
+        return loss, z2, z3
 
     def barrier():
         if use_dist:
@@ -528,7 +563,7 @@ def main():
             prof.enable()
         t0 = time.perf_counter()
         for i in range(n_steps):
-            loss = step(n_warm + i)
+            last = step(n_warm + i)
             if use_marks:
                 marks[i + 1].record()
             if args.lead_probe:       # how many steps is the host ahead of the GPU? (0 = the GPU waits for the host)
@@ -554,11 +589,11 @@ def main():
             t = torch.tensor([dt_], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_ = t.item()
-        return dt_, t_enq, ms, loss
+        return dt_, t_enq, ms, last
 
     sync_note = None
     try:
-        dt, t_enqueue, step_ms, loss = timed_region(args.warmup, args.steps, profile=args.host_profile, kernel_timers=args.timers_in_main)
+        dt, t_enqueue, step_ms, last = timed_region(args.warmup, args.steps, profile=args.host_profile, kernel_timers=args.timers_in_main)
     except Exception as exc:      # noqa: BLE001 - a data-parallel run must still end in a line
         if not (use_dist and headline_sync):
             raise
@@ -573,18 +608,26 @@ def main():
         except Exception:         # noqa: BLE001
             pass
         adist.setup([pna, net], loss_fn, sync_bn=False, broadcast=False)
-        dt, t_enqueue, step_ms, loss = timed_region(args.warmup, args.steps, kernel_timers=args.timers_in_main)
-    if not args.timers_in_main:
+        dt, t_enqueue, step_ms, last = timed_region(args.warmup, args.steps, kernel_timers=args.timers_in_main)
+    loss = last[0]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (loss, embeddings) and left behind (model state after the optimizer step) -
+        # taken before anything else runs on the models
+        dump_outputs(args.dump_outputs, dict(loss=loss.detach().reshape(1).cpu().numpy(), pna_embeddings=last[1].detach().cpu().numpy(),
+                                             net3d_embeddings=last[2].detach().cpu().numpy(), pna_state=model_state(pna),
+                                             net3d_state=model_state(net)))
+    del last
+    if args.full and not args.timers_in_main:
         # the in-step K4 figure (roofline.achieved): a short window of the SAME steps right after the timed region, its K4 forward
         # dispatches carrying timing events - kept out of the headline loop, which runs the production launch path (round 5's
         # judge: host_enqueue of the main region 1.99 ms against 1.28 ms in the extra windows; profiles/r06_host_main_vs_extra.txt)
         timed_region(2, min(10, max(args.steps, 1)), kernel_timers=True)
     timers, ops.KERNEL_TIMERS = ops.KERNEL_TIMERS or {}, None
     other_bn = None
-    if use_dist and sync_note is None:
+    if args.full and use_dist and sync_note is None:
         # the other BatchNorm mode on the same models and batches (same number of steps; the weights keep training)
         adist.setup([pna, net], loss_fn, sync_bn=not headline_sync, broadcast=False)
-        o_dt, o_enq, o_ms, o_loss = timed_region(min(args.warmup, 10), args.steps)
+        o_dt, o_enq, o_ms, (o_loss, *_) = timed_region(min(args.warmup, 10), args.steps)
         other_bn = dict(sync_bn=not headline_sync, value=round(args.steps * args.batch * world / o_dt, 1), unit='molecules/s',
                         ms_per_step=round(o_dt / args.steps * 1e3, 3), ms_per_step_median=round(o_ms[len(o_ms) // 2], 3),
                         host_enqueue_ms_per_step=round(o_enq / args.steps * 1e3, 3), final_loss=round(float(o_loss.item()), 5),
@@ -597,7 +640,7 @@ def main():
     # fresh batch from the flat dataset on the host (vectorised numpy), copies it and builds the 3D graphs on device
     with_assembly = with_assembly_inline = None
     with_prefetch = {}
-    if (not use_dist or world == 1) and not qmugs:
+    if args.full and (not use_dist or world == 1) and not qmugs:
         dataset = importlib.import_module('3dinfomax_amd.dataset')
         all_mols = [m for _, _, shard in batches for m in shard]
         flat = dataset.FlatMolDataset(all_mols)
@@ -684,7 +727,7 @@ def main():
     # roofline of the dominant HBM kernel: K4 PNA aggregation (forward), algorithmic bytes per SURVEY.md 8d
     ev = timers.get('pna_aggregate_fwd', [])
     roof = None
-    if ev:
+    if args.full and ev:
         ms = np.array([a.elapsed_time(b) for a, b, *_ in ev])
         byts = np.array([4.0 * E * F + 4.0 * N * W + 4.0 * (N + 1) for _, _, N, E, F, W in ev])
         achieved = float(byts.sum() / (ms.sum() * 1e-3) / 1e9)
@@ -810,7 +853,7 @@ def main():
                                              'figures in DESIGN.md section 4')
     # per-collective times of the data-parallel step (20 back-to-back calls per event pair, after the timed region)
     collectives = None
-    if use_dist:
+    if args.full and use_dist:
         def timed_coll(fn, reps=20):
             fn()
             torch.cuda.synchronize()
@@ -866,7 +909,7 @@ def main():
         mol_per_s = args.steps * B * world / dt
         out = dict(metric='molecules/sec pretraining step (PNA+Net3D, QM9-50k); PNA-agg HBM GB/s vs peak',
                    value=round(mol_per_s, 1), unit='molecules/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=round(dt / args.steps * 1e3, 3), higher_is_better=True, scaling='weak',
+                   ms_per_step=round(dt / args.steps * 1e3, 3), higher_is_better=True, scaling='weak', full=args.full,
                    vs_baseline=None, dtype='f32' if args.dtype == 'fp32' else 'bf16', data='synthetic',
                    config=dict(precision=(FP32_PRODUCTS[ops.get_fp32_products()] if args.dtype == 'fp32' else
                                           'bf16 MATMUL mode - not bf16 storage: every GEMM multiplies bf16-rounded operands on '
@@ -911,10 +954,10 @@ def main():
             out['parity'] = ('reference-equal: BatchNorm statistics over the global batch, all-gathered negatives' if headline_sync
                              else 'NOT reference-equal: per-rank BatchNorm statistics'
                                   + (' (fallback: the synchronised step failed at run time)' if sync_note else ' (--local-bn)'))
-        if world == 1 and not use_dist and not qmugs and not args.no_extra_workloads and args.dtype == 'fp32':
+        if args.full and world == 1 and not use_dist and not qmugs and not args.no_extra_workloads and args.dtype == 'fp32':
             del batches[1:]
             out['config']['extra_workloads'] = extra_workloads(amd, ops, dev, args.depth)
-        if world == 1 and not args.no_cpu_baseline and not qmugs:
+        if args.full and world == 1 and not args.no_cpu_baseline and not qmugs:
             out['cpu_baseline'] = cpu_baseline(batches[0][2], args.depth, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -88,3 +88,23 @@ def test_bench_under_a_launcher_does_not_launch_again():
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
     assert out['ranks_seen'] == 2 and 'without a launcher' not in r.stderr
+
+
+def test_dump_outputs_are_float32_and_capped_by_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array lands as <name>.npy in float32; over the limit, the large arrays become the same seeded sample
+    on every run, and the files stay under 64 MB in all."""
+    import numpy as np
+    bench = _bench()
+    small = dict(loss=np.array([1.5], dtype=np.float64), z=np.arange(12, dtype=np.float32).reshape(3, 4))
+    bench.dump_outputs(str(tmp_path / 'small'), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / 'small' / f'{k}.npy')
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    big = dict(a=np.arange(20 << 20, dtype=np.float32), b=np.ones(3))
+    for d in ('big1', 'big2'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(tmp_path / 'big1' / f) for f in os.listdir(tmp_path / 'big1'))
+    assert total < 64e6
+    a1, a2 = np.load(tmp_path / 'big1' / 'a.npy'), np.load(tmp_path / 'big2' / 'a.npy')
+    assert np.array_equal(a1, a2) and a1.size < big['a'].size and np.all(np.diff(a1) >= 0)
+    assert np.array_equal(np.load(tmp_path / 'big1' / 'b.npy'), big['b'])

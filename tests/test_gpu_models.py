@@ -971,7 +971,7 @@ def test_num_batches_tracked_counts_forward_passes(amd, monkeypatch, composite):
     assert len(counters) > 5 and all(v == 3 for _, v in counters), counters
 
 
-def test_process_level_switches_give_the_same_bits():
+def test_process_level_switches_give_the_same_bits(tmp_path):
     """Switches that are read once per process (-> subprocesses): the weight-gradient side stream of the backward
     composites off / with two forks, freshly allocated parameter gradients, the in-launch finalisation off - three
     optimisation steps end in the same bits as the default."""
@@ -1015,7 +1015,7 @@ def test_process_level_switches_give_the_same_bits():
                 'autograd_param_grads': {'I3D_DIRECT_PARAM_GRADS': '0'}}
     variants = {k: v for k, v in variants.items() if v is not None}
     for name, env in variants.items():
-        path = f'/tmp/i3d_switch_{name}.pt'
+        path = str(tmp_path / f'switch_{name}.pt')
         subprocess.run([sys.executable, '-c', code, path], check=True, env=dict(os.environ, **env), timeout=600)
         res[name] = torch.load(path)
     assert len(res['default']) > 50

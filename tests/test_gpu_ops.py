@@ -577,7 +577,7 @@ def test_bn_bwd_one_launch_against_the_two_pass_kernels(rows, feat, act, post):
     assert rel_err(gg1.cpu(), gg2.cpu()) < 2e-6 and rel_err(gb1.cpu(), gb2.cpu()) < 2e-6
 
 
-def test_in_launch_finalisation_matches_separate_launch():
+def test_in_launch_finalisation_matches_separate_launch(tmp_path):
     """The default (stage 2 of the column reductions inside the stage-1 launch, last arrivers reduce) gives the same bits as
     separate finalise launches (I3D_FUSED_FINAL=0); the switch is read once per process -> subprocess."""
     import os
@@ -601,7 +601,7 @@ def test_in_launch_finalisation_matches_separate_launch():
         "torch.save([t.cpu() for t in out], sys.argv[1])\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     for mode in ('0', '1'):
-        path = f'/tmp/i3d_fused_final_{mode}.pt'
+        path = str(tmp_path / f'fused_final_{mode}.pt')
         env = dict(os.environ, I3D_FUSED_FINAL=mode)
         subprocess.run([sys.executable, '-c', code, path], check=True, env=env, timeout=300)
         res[mode] = torch.load(path)

@@ -65,52 +65,76 @@ def test_launcher_rebinds_plugin_names_without_editing_the_script(tmp_path):
     assert out['optimizer'].startswith('torch.optim') and out['loss'] == 'commons_losses' and out['model'] == '3dinfomax_amd.pna'
 
 
-REFERENCE_TRAIN = '/root/reference/train.py'
+# the module layout the launcher relies on (reference train.py:50-56 star-imports; trainer/trainer.py:266-270 looks the model class
+# up the same way): where each plugin name is defined, and the star-import that brings it into train.py
+LAYOUT = {'models/pna.py': ['PNA'], 'models/net3d.py': ['Net3D'], 'models/pna_original.py': ['PNAOriginal', 'PNAOriginalSimple'],
+          'commons/losses.py': ['NTXent', 'NTXentMultiplePositives'],
+          'datasets/custom_collate.py': ['contrastive_collate', 'conformer_collate', 'graph_collate']}
+LOOKUP_KEYS = ('model_type', 'model3d_type', 'loss_func', 'optimizer', 'collate_function')
 
 
-def test_launcher_against_the_reference_train_py_itself():
-    """Build container only (the reference tree does not travel to the GPU box): the launcher's two assumptions about the
-    REAL file - (1) it has a top-level `if __name__ == '__main__':` block main_block() can lift, (2) every plugin name the
-    package exports that train.py resolves at call time through `globals()[...]` reaches train.py's namespace through one
-    of its star-imports (so rebinding that namespace is what the lookups see) - checked on its syntax tree, without
-    executing it (its imports need dgl / ogb / rdkit)."""
+def test_launcher_on_a_script_with_the_reference_layout(tmp_path):
+    """The launcher's two assumptions about a script laid out like the reference's train.py - (1) it has a top-level
+    `if __name__ == '__main__':` block main_block() can lift, (2) every plugin name the package exports that the script resolves
+    at call time through `globals()[args.<key>]` reaches its namespace through one of its star-imports of the reference's
+    modules (models, commons.losses, datasets.custom_collate, torch.optim), so rebinding that namespace is what the lookups see,
+    also in trainer.trainer - checked end to end on a stand-in tree with that layout (the reference itself is not part of the
+    repository)."""
     import ast
+    import json
 
-    import pytest
-    if not os.path.exists(REFERENCE_TRAIN):
-        pytest.skip('reference tree not present')
     sys.path.insert(0, ROOT)
     launcher = importlib.import_module('launch_reference')
-    with open(REFERENCE_TRAIN) as f:
-        src = f.read()
-    code = launcher.main_block(src, REFERENCE_TRAIN)
-    assert 'get_arguments' in code.co_names and 'train' in code.co_names      # reference train.py:644-700
+    for rel, names in LAYOUT.items():
+        path = tmp_path / rel
+        path.parent.mkdir(exist_ok=True)
+        (path.parent / '__init__.py').touch()
+        path.write_text(''.join(f'class {n}:\n    origin = "reference"\n' if n[0].isupper() else
+                                f'def {n}(batch):\n    return "reference"\n' for n in names))
+    (tmp_path / 'models' / '__init__.py').write_text(
+        'from models.pna import *\nfrom models.net3d import *\nfrom models.pna_original import *\n')
+    (tmp_path / 'trainer').mkdir()
+    (tmp_path / 'trainer' / '__init__.py').touch()
+    (tmp_path / 'trainer' / 'trainer.py').write_text('from models import *\n\n\ndef model_class(name):\n    return globals()[name]\n')
+    script = tmp_path / 'train.py'
+    script.write_text(textwrap.dedent('''
+        import argparse, json, sys
+        from models import *
+        from commons.losses import *
+        from datasets.custom_collate import *
+        from torch.optim import *
+        from trainer.trainer import model_class
+
+        def get_arguments():
+            return argparse.Namespace(model_type='PNA', model3d_type='Net3D', loss_func='NTXent', optimizer='Adam',
+                                      collate_function='contrastive_collate')
+
+        def train(args):
+            out = {k: globals()[getattr(args, k)].__module__ for k in %r}
+            out.update({n: globals()[n].__module__ for n in %r})
+            out['trainer.trainer'] = model_class(args.model_type).__module__
+            print('RESULT ' + json.dumps(out))
+
+        if __name__ == '__main__':
+            args = get_arguments()
+            train(args)
+    ''' % (LOOKUP_KEYS, [n for names in LAYOUT.values() for n in names])))
+    src = script.read_text()
+    code = launcher.main_block(src, str(script))
+    assert 'get_arguments' in code.co_names and 'train' in code.co_names
     tree = ast.parse(src)
     stars = [n.module for n in tree.body if isinstance(n, ast.ImportFrom) and any(a.name == '*' for a in n.names)]
-    # the star-imports the plugin's names arrive through (train.py:50-56)
     for mod in ('models', 'commons.losses', 'datasets.custom_collate', 'torch.optim'):
         assert mod in stars, (mod, stars)
-    # every globals()[args.<key>] lookup of the file: the keys the plugin must serve
-    lookups = set()
-    for node in ast.walk(tree):
-        if (isinstance(node, ast.Subscript) and isinstance(node.value, ast.Call) and isinstance(node.value.func, ast.Name)
-                and node.value.func.id == 'globals'):
-            key = node.slice
-            if isinstance(key, ast.Attribute):
-                lookups.add(key.attr)
-    assert {'model_type', 'model3d_type', 'loss_func', 'optimizer', 'collate_function'} <= lookups, lookups
     names = launcher.plugin_names()
     for n in ('PNA', 'Net3D', 'NTXent', 'NTXentMultiplePositives', 'Adam', 'contrastive_collate', 'conformer_collate',
               'graph_collate', 'PNAOriginal', 'PNAOriginalSimple'):
         assert n in names, n
-    # the reference defines each of them in a module one of those star-imports covers
-    ref_root = os.path.dirname(REFERENCE_TRAIN)
-    defined = {}
-    for rel in ('models/pna.py', 'models/net3d.py', 'models/pna_original.py', 'commons/losses.py', 'datasets/custom_collate.py'):
-        with open(os.path.join(ref_root, rel)) as f:
-            for node in ast.parse(f.read()).body:
-                if isinstance(node, (ast.ClassDef, ast.FunctionDef)):
-                    defined[node.name] = rel
-    for n in ('PNA', 'Net3D', 'NTXent', 'NTXentMultiplePositives', 'contrastive_collate', 'conformer_collate', 'graph_collate',
-              'PNAOriginal', 'PNAOriginalSimple'):
-        assert n in defined, n
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'launch_reference.py'), str(script)], capture_output=True, text=True,
+                       cwd=str(tmp_path), env=dict(os.environ, PYTHONPATH=ROOT), timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('RESULT ')][0][len('RESULT '):])
+    assert set(LOOKUP_KEYS) <= set(out)
+    for k, module in out.items():
+        assert module.startswith('3dinfomax_amd.'), (k, module)
+    assert script.read_text() == src

@@ -5,18 +5,18 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/r06
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python $ROOT/bench.py"
+B="python $ROOT/bench.py --full"
 $B > $OUT/bench.json 2> $OUT/bench.err
 $B --depth 7 --no-cpu-baseline --no-families --no-extra-workloads > $OUT/bench_depth7.json 2>/dev/null
 $B --batch 4096 --no-cpu-baseline --no-families --no-extra-workloads > $OUT/bench_B4096.json 2>/dev/null
 $B --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2>/dev/null
 $B --workload qmugs --no-cpu-baseline > $OUT/bench_qmugs.json 2>/dev/null
 $B --workload qmugs --dtype bf16 --no-cpu-baseline > $OUT/bench_qmugs_bf16.json 2>/dev/null
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 $ROOT/bench.py --gpus 1 --force-dist \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 $ROOT/bench.py --gpus 1 --full --force-dist \
     --no-cpu-baseline --no-families --no-extra-workloads --steps 100 --warmup 20 2>/dev/null | tail -1 > $OUT/bench_force_dist_world1.json
-I3D_SYNC_PROVIDER=rccl python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 $ROOT/bench.py --gpus 1 \
+I3D_SYNC_PROVIDER=rccl python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 $ROOT/bench.py --gpus 1 --full \
     --force-dist --no-cpu-baseline --no-families --no-extra-workloads --steps 100 --warmup 20 2>/dev/null | tail -1 > $OUT/bench_force_dist_world1_rccl.json
-python $ROOT/bench.py --gpus 2 --backend gloo \
+python $ROOT/bench.py --gpus 2 --full --backend gloo \
     --no-cpu-baseline --no-families --no-extra-workloads --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_dp2_gloo_one_gpu.json
 python $ROOT/tools/wgrad_bench.py > $OUT/wgrad_bench.txt 2>&1
 python $ROOT/tools/fused_gemm_bench.py > $OUT/fused_gemm_bench.txt 2>&1

@@ -21,7 +21,7 @@ for steps in 25 300; do
   run "steps $steps marks pool1"                              --steps $steps --warmup $w --pool 1
 done
 done
-python bench.py --no-cpu-baseline --no-families --steps 50 --warmup 10 2>/dev/null | grep "^{" | tail -1 | python -c "
+python bench.py --full --no-cpu-baseline --no-families --steps 50 --warmup 10 2>/dev/null | grep "^{" | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); c=j['config']
 print('default line: ms_per_step %.3f host_enqueue %.3f' % (j['ms_per_step'], c['host_enqueue_ms_per_step']))
