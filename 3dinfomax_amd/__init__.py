@@ -5,8 +5,8 @@ The package name starts with a digit, so import it with importlib.import_module(
 the alias module `infomax3d_amd` at the repository root.
 """
 from .graph import (BatchedMolGraph, GraphIndex, as_batched_graph, batch, bond_graph, complete_graph,  # noqa: F401
-                    conformer_collate, contrastive_collate, graph_collate, s_norm_contrastive_collate,
-                    s_norm_graph_collate)
+                    conformer_collate, contrastive_collate, graph_collate, pairwise_distance_collate,
+                    s_norm_contrastive_collate, s_norm_graph_collate)
 from . import synth  # noqa: F401
 
 
@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in ('NTXent', 'NTXentMultiplePositives'):
         from . import losses
         return getattr(losses, name)
+    if name == 'DistancePredictor':
+        from . import distance_predictor
+        return distance_predictor.DistancePredictor
     if name in ('FCLayer', 'MLP'):
         from . import layers
         return getattr(layers, name)
@@ -53,4 +56,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMultiplePositives', 'FCLayer', 'MLP', 'AtomEncoder', 'BondEncoder', 'contrastive_collate',
            'conformer_collate', 'graph_collate', 's_norm_graph_collate', 's_norm_contrastive_collate', 'BatchedMolGraph', 'batch', 'bond_graph', 'complete_graph', 'Adam', 'PositiveSimilarity',
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
-           'BatchVariance', 'DimensionCovariance']
+           'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate']

@@ -320,6 +320,15 @@ _SIGNATURES = {
     'i3d_contrastive_rowstats': (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, _P, _P]),
     'i3d_cov_rowstats': (c_int, [_P, _P, c_int, c_int, _P, _P]),
     'i3d_complete_graph_build': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'i3d_mha_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    'i3d_mha_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    'i3d_ln_res_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P]),
+    'i3d_ln_res_partial_floats': (c_long, [c_int, c_int]),
+    'i3d_ln_res_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    'i3d_pair_sum_fwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_pair_sum_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_pair_norm_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_pair_norm_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
 }
 
 _lib = None

@@ -70,6 +70,19 @@ class FlatMolDataset:
         g2, xyz, graph_ptr_dev, n, bnn = self.assemble_2d(ids, device, pin)
         return [g2], [complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)]
 
+    def assemble_distance(self, ids, device, pin=False):
+        """-> ([g2d, pairwise_indices [2, P], mask [B, maxN]], distances [P, 1]) on `device`: the layout
+        `pairwise_distance_collate` returns (reference datasets/custom_collate.py:65-78), with the pairs, their distances and the
+        pair graph's kernel index built on the device by the complete-graph kernel (the pairs are its edges, in its order)."""
+        g2, xyz, graph_ptr_dev, n, bnn = self.assemble_2d(ids, device, pin)
+        g3 = complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)
+        src, dst = g3.edges()
+        pairwise_indices = torch.stack([src, dst])
+        pairwise_indices._i3d_pair_index = g3.index()       # distance_predictor.pair_index
+        n_t = torch.from_numpy(np.asarray(n, dtype=np.int64))
+        mask = (torch.arange(int(n_t.max()))[None, :] >= n_t[:, None]).to(xyz.device)
+        return [g2, pairwise_indices, mask], g3.edata['d']
+
     def assemble_2d(self, ids, device, pin=False):
         """The bond-graph half (pure numpy + three H2D copies; also usable on the CPU for tests)."""
         return host_batch_to_device(self.assemble_host(ids), device, pin)

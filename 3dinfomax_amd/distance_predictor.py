@@ -1,0 +1,259 @@
+"""Distance-prediction baseline on the MI355X kernels - drop-in for reference models/distance_predictor.py.
+
+Same class name, constructor and sub-module names (`node_gnn`, `transformer_layer`, `node_projection_net`, `distance_net`), hence
+the same state_dict keys and shapes: reference checkpoints load strict.  `torch.nn.TransformerEncoderLayer` is kept as the
+PARAMETER CONTAINER of the attention block (its initialisation, its place in the seed order); its forward is never called.
+
+The arithmetic is the reference's, re-laid for the hardware:
+  * the transformer runs on the compact node rows of the batch, the molecules given by the graph's node offsets, instead of the
+    padded [B, maxN, H] batch with a key padding mask (reference distance_predictor.py:50-58): in_proj / out_proj / linear1 /
+    linear2 are the package's fused GEMMs (layers.FCFn), the attention is csrc/distance.hip (one workgroup per molecule and
+    head, online softmax), each residual add sits inside its LayerNorm;
+  * distance_net of one Linear (the blessed configuration): f([h_i|h_j]) + f([h_j|h_i]) = u_i + u_j + 2b with u = (W_a + W_b) h,
+    so the head is an [N, H] x [H, T] product and a pair kernel instead of two [P, 2H] x [2H, T] products;
+  * the per-node sums of the pair gradients are segment sums over the pair graph's kernel index (graph.GraphIndex): fixed
+    order, no atomics.
+"""
+import math
+
+import torch
+from torch import nn
+
+from . import ops, tape
+from .graph import as_batched_graph, build_index
+from .layers import MLP, FCFn, FCSpec, bn_counter_scope
+from .pna import PNAGNN
+
+_LINEAR = FCSpec(None, None)
+_RELU = FCSpec('relu', None)
+
+
+def pair_index(pairwise_indices, graph):
+    """The kernel index (graph.GraphIndex) of the pair graph whose edges are `pairwise_indices` [2, P] over the nodes of `graph`.
+    A batch assembled on the device (dataset.FlatMolDataset.assemble_distance) carries it; otherwise it is built once on the
+    host and kept on the tensor."""
+    idx = getattr(pairwise_indices, '_i3d_pair_index', None)
+    if idx is None:
+        g = as_batched_graph(graph)
+        pi = pairwise_indices.detach().cpu().numpy()
+        idx = build_index(pi[0], pi[1], g.number_of_nodes(), g.batch_num_nodes().cpu().numpy()).to(pairwise_indices.device)
+        pairwise_indices._i3d_pair_index = idx
+    return idx
+
+
+class _MHAFn(torch.autograd.Function):
+    """softmax(q k^T / sqrt(dh)) v per molecule and head from the [N, 3H] in_proj rows (csrc/distance.hip)"""
+
+    @staticmethod
+    def forward(ctx, qkv, index, nhead):
+        qkv = qkv.contiguous()
+        scale = 1.0 / math.sqrt(qkv.shape[1] // 3 // nhead)
+        out, lse = ops.mha_fwd(qkv, index.graph_ptr, index.num_graphs, nhead, scale)
+        ctx.cfg = (index, nhead, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, out, lse = ctx.saved_tensors
+        index, nhead, scale = ctx.cfg
+        return ops.mha_bwd(qkv, out, grad_out.contiguous(), lse, index.graph_ptr, index.num_graphs, nhead, scale), None, None
+
+
+class _LayerNormResFn(torch.autograd.Function):
+    """LayerNorm(x + r) * gamma + beta (csrc/distance.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, r, gamma, beta, eps):
+        x, r = x.contiguous(), r.contiguous()
+        y, mean, rstd = ops.ln_res_fwd(x, r, gamma, beta, eps)
+        ctx.save_for_backward(x, r, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, r, gamma, mean, rstd = ctx.saved_tensors
+        gz, gg, gb = ops.ln_res_bwd(grad_y.contiguous(), x, r, gamma, mean, rstd)
+        return gz, gz, gg, gb, None
+
+
+class _PairSumHeadFn(torch.autograd.Function):
+    """softplus(f([h_i|h_j]) + f([h_j|h_i])) for f = Linear(2H -> T), W = [W_a | W_b]: u = h W_a^T + h W_b^T, then the pair kernel"""
+
+    @staticmethod
+    def forward(ctx, h, W, b, pidx):
+        h = h.contiguous()
+        H = h.shape[1]
+        u = ops.gemm(h, W[:, :H], trans_b=True)
+        ops.gemm(h, W[:, H:], trans_b=True, out=u, accumulate=True)
+        ctx.pidx = pidx
+        ctx.save_for_backward(h, W, b, u)
+        return ops.pair_sum_fwd(u, b, pidx)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, W, b, u = ctx.saved_tensors
+        H = h.shape[1]
+        du = ops.pair_sum_bwd(grad_out.contiguous(), u, b, ctx.pidx)
+        gW = torch.empty_like(W)
+        ops.gemm(du, h, trans_a=True, out=gW[:, :H])
+        ops.gemm(du, h, trans_a=True, out=gW[:, H:])
+        gb = ops.colsum(du)           # sum over nodes of du = 2 x sum over pairs: d(2b)/db
+        gh = ops.gemm(du, W[:, :H])
+        ops.gemm(du, W[:, H:], out=gh, accumulate=True)
+        return gh, gW, gb, None
+
+
+class _PairNormFn(torch.autograd.Function):
+    """||p_i - p_j||_2 per pair, [P, 1]"""
+
+    @staticmethod
+    def forward(ctx, p, pidx):
+        p = p.contiguous()
+        d = ops.pair_norm_fwd(p, pidx)
+        ctx.pidx = pidx
+        ctx.save_for_backward(p, d)
+        return d
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        p, d = ctx.saved_tensors
+        return ops.pair_norm_bwd(grad_out.contiguous(), p, d, ctx.pidx), None
+
+
+class _PairConcatFn(torch.autograd.Function):
+    """[h_a | h_b] per pair in the pair graph's epos order: (a, b) = (src, dst), or (dst, src) with `swap` (segment sums of one row)"""
+
+    @staticmethod
+    def forward(ctx, h, pidx, swap):
+        h = h.contiguous()
+        P, H = pidx.num_edges, h.shape[1]
+        one = _ranges(P, h.device)
+        out = torch.empty(P, 2 * H, dtype=torch.float32, device=h.device)
+        first, second = (pidx.dst_s, pidx.src_s) if swap else (pidx.src_s, pidx.dst_s)
+        ops.segment_sum(h, one, first, P, out=out[:, :H])
+        ops.segment_sum(h, one, second, P, out=out[:, H:])
+        ctx.cfg = (pidx, swap, H)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pidx, swap, H = ctx.cfg
+        g = g.contiguous()
+        gs, gd = (g[:, H:], g[:, :H]) if swap else (g[:, :H], g[:, H:])
+        return ops._pair_node_sums(gs, gd, pidx), None, None
+
+
+class _SoftplusSumToPairsFn(torch.autograd.Function):
+    """softplus(a + b), rows permuted from the pair graph's epos order to pair-id order"""
+
+    @staticmethod
+    def forward(ctx, a, b, pidx):
+        x = ops.add(a.contiguous(), b.contiguous())
+        ctx.pidx = pidx
+        ctx.save_for_backward(x)
+        return ops.gather_rows(ops.act_fwd(x, 'softplus'), pidx.inv_perm)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        ge = ops.act_bwd(ops.gather_rows(g.contiguous(), ctx.pidx.perm), x, 'softplus')
+        return ge, ge, None
+
+
+_ranges_cache = {}
+
+
+def _ranges(n, device):
+    """int32 [0, 1, ..., n]: the row pointer of n one-row segments"""
+    key = (n, str(device))
+    t = _ranges_cache.get(key)
+    if t is None:
+        if len(_ranges_cache) > 64:
+            _ranges_cache.clear()
+        t = _ranges_cache[key] = torch.arange(n + 1, dtype=torch.int32, device=device)
+    return t
+
+
+class DistancePredictor(nn.Module):
+    """reference models/distance_predictor.py:13-88.  forward(graph, pairwise_indices, mask) -> [P, target_dim]; as in the
+    reference, graph.ndata['feat'] is left holding the node state the pair head read.  `mask` ([B, maxN], True on padding) is
+    accepted for the reference's signature; the molecules are taken from the graph's node offsets."""
+
+    def __init__(self, target_dim, pna_args, projection_dim=3, distance_net=False, projection_layers=1, transformer_layer=True,
+                 nhead=16, dim_feedforward=256, activation='relu', **kwargs):
+        super().__init__()
+        hidden_dim = pna_args['hidden_dim']
+        dropout = pna_args.get('dropout', 0.0)
+        if transformer_layer:
+            if dropout:
+                raise NotImplementedError(f'transformer_layer with dropout={dropout} (pna_args dropout): the fused attention block '
+                                          'has no dropout; use dropout 0')
+            act = activation if isinstance(activation, str) else getattr(activation, '__name__', type(activation).__name__)
+            if str(act).lower() != 'relu':
+                raise NotImplementedError(f'transformer_layer with activation={activation!r}: the fused feed-forward block takes '
+                                          'ReLU only')
+            if hidden_dim % nhead:
+                raise ValueError(f'nhead={nhead} does not divide hidden_dim={hidden_dim}')
+            if hidden_dim // nhead > 128:
+                raise NotImplementedError(f'nhead={nhead}: head width hidden_dim / nhead = {hidden_dim // nhead} above 128')
+            if projection_dim > 0 and not distance_net:
+                raise ValueError(f'projection_dim={projection_dim} with transformer_layer=True and distance_net=False: the '
+                                 f'reference feeds the {projection_dim}-wide projection into a transformer of width {hidden_dim} '
+                                 '(size mismatch at reference distance_predictor.py:54)')
+        if distance_net and projection_layers > 1 and projection_dim <= 0:
+            raise ValueError(f'distance_net with projection_layers={projection_layers} needs projection_dim > 0 (the hidden width '
+                             'of distance_net)')
+        self.node_gnn = PNAGNN(**pna_args)
+        self.transformer_layer = transformer_layer
+        if transformer_layer:
+            self.transformer_layer = nn.TransformerEncoderLayer(d_model=hidden_dim, dim_feedforward=dim_feedforward, nhead=nhead,
+                                                                batch_first=True, dropout=dropout, activation=activation)
+        if projection_dim > 0:
+            self.node_projection_net = MLP(in_dim=hidden_dim, hidden_size=32, mid_batch_norm=True, out_dim=projection_dim,
+                                           layers=projection_layers)
+        else:
+            self.node_projection_net = None
+        if distance_net:
+            self.distance_net = MLP(in_dim=hidden_dim * 2, hidden_size=projection_dim, mid_batch_norm=True, out_dim=target_dim,
+                                    layers=projection_layers)
+        else:
+            self.distance_net = None
+        self.nhead = nhead
+
+    def forward(self, graph, pairwise_indices, mask=None):
+        g = as_batched_graph(graph)
+        pidx = pair_index(pairwise_indices, g)
+        with bn_counter_scope():
+            return tape.run_model(self, lambda: self._forward(g, pidx))
+
+    def _forward(self, g, pidx):
+        self.node_gnn(g)
+        h = g.ndata['feat']
+        if self.node_projection_net is not None and self.distance_net is None:
+            h = self.node_projection_net(h)
+        if self.transformer_layer:
+            h = self._transformer(h, g.index())
+        g.ndata['feat'] = h
+        if self.distance_net is None:
+            return tape.apply(_PairNormFn, h, pidx)
+        fcs = self.distance_net.fully_connected
+        if len(fcs) == 1:
+            W, b = fcs[0].hot()[:2]
+            return tape.apply(_PairSumHeadFn, h, W, b, pidx)
+        # several layers (BatchNorm inside): the reference's two calls on the [P, 2H] concatenations, two sets of statistics
+        y1 = self.distance_net(tape.apply(_PairConcatFn, h, pidx, False))
+        y2 = self.distance_net(tape.apply(_PairConcatFn, h, pidx, True))
+        return tape.apply(_SoftplusSumToPairsFn, y1, y2, pidx)
+
+    def _transformer(self, x, index):
+        """post-norm TransformerEncoderLayer: x = norm1(x + out_proj(attn(x))); x = norm2(x + linear2(relu(linear1(x))))"""
+        t = self.transformer_layer
+        sa = t.self_attn
+        qkv = tape.apply(FCFn, x, sa.in_proj_weight, sa.in_proj_bias, None, None, None, _LINEAR)
+        att = tape.apply(_MHAFn, qkv, index, self.nhead)
+        a = tape.apply(FCFn, att, sa.out_proj.weight, sa.out_proj.bias, None, None, None, _LINEAR)
+        x = tape.apply(_LayerNormResFn, x, a, t.norm1.weight, t.norm1.bias, t.norm1.eps)
+        f = tape.apply(FCFn, x, t.linear1.weight, t.linear1.bias, None, None, None, _RELU)
+        f = tape.apply(FCFn, f, t.linear2.weight, t.linear2.bias, None, None, None, _LINEAR)
+        return tape.apply(_LayerNormResFn, x, f, t.norm2.weight, t.norm2.bias, t.norm2.eps)

@@ -250,6 +250,19 @@ def graph_collate(batch_items):
     return [batch(graphs)], targets
 
 
+def pairwise_distance_collate(batch_items):
+    """Mirror of reference datasets/custom_collate.py:65-78: items (graph, pairwise_indices [2, p], distances [p, 1]) ->
+    ([batched graph, pairwise_indices [2, P] with every molecule's node offset added, mask [B, maxN] True on padding],
+    distances [P, 1]).  The items' index tensors are not modified."""
+    graphs, pairwise_indices, distances = map(list, zip(*batch_items))
+    g = batch(graphs)
+    n_atoms = g.batch_num_nodes()
+    offsets = torch.cumsum(n_atoms, 0) - n_atoms
+    pidx = torch.cat([torch.as_tensor(p) + off for p, off in zip(pairwise_indices, offsets.tolist())], dim=-1)
+    mask = torch.arange(int(n_atoms.max()), device=distances[0].device)[None, :] >= n_atoms[:, None]
+    return [g, pidx, mask], torch.cat(distances)
+
+
 def _snorm_n(graphs):
     """sqrt(1 / n_atoms) per node, [N, 1] (reference datasets/custom_collate.py:45-47, 96-98: the graph-size
     normalisation factor of the original PNA, models/pna_original.py:258-259)."""

@@ -783,3 +783,106 @@ def wgrad_multi(problems, outputs):
     dev = problems[0]['A'].device
     check(L.i3d_wgrad_multi(pa, len(problems), oa, len(outputs), _p(_gemm_workspace(dev)), GEMM_WORKSPACE_BYTES, _stream()),
           'i3d_wgrad_multi')
+
+
+# ---- distance-prediction baseline (csrc/distance.hip) ----------------------------------------------------------------
+def mha_fwd(qkv, graph_ptr, num_graphs, nhead, scale):
+    """per-molecule multi-head self-attention: qkv [N, 3H] (in_proj output) -> (out [N, H], lse [N, nhead])"""
+    _chk(qkv)
+    _chk(graph_ptr, torch.int32)
+    N, H = qkv.shape[0], qkv.shape[1] // 3
+    out = torch.empty(N, H, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(N, nhead, dtype=torch.float32, device=qkv.device)
+    check(_lib.load().i3d_mha_fwd(_p(qkv), _p(graph_ptr), num_graphs, N, H, nhead, float(scale), _p(out), _p(lse), _stream()),
+          'i3d_mha_fwd')
+    return out, lse
+
+
+def mha_bwd(qkv, out, grad_out, lse, graph_ptr, num_graphs, nhead, scale):
+    """-> grad_qkv [N, 3H]"""
+    for t in (qkv, out, grad_out, lse):
+        _chk(t)
+    N, H = out.shape
+    delta = torch.empty(N, nhead, dtype=torch.float32, device=qkv.device)
+    grad_qkv = torch.empty_like(qkv)
+    check(_lib.load().i3d_mha_bwd(_p(qkv), _p(out), _p(grad_out), _p(lse), _p(graph_ptr), num_graphs, N, H, nhead, float(scale),
+                                  _p(delta), _p(grad_qkv), _stream()), 'i3d_mha_bwd')
+    return grad_qkv
+
+
+def ln_res_fwd(x, r, gamma, beta, eps):
+    """y = LayerNorm(x + r) -> (y, mean [rows], rstd [rows])"""
+    for t in (x, r, gamma, beta):
+        _chk(t)
+    rows, feat = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    check(_lib.load().i3d_ln_res_fwd(_p(x), _p(r), _p(gamma), _p(beta), rows, feat, float(eps), _p(y), _p(mean), _p(rstd),
+                                     _stream()), 'i3d_ln_res_fwd')
+    return y, mean, rstd
+
+
+def ln_res_bwd(grad_y, x, r, gamma, mean, rstd):
+    """-> (grad of x + r [rows, feat], grad_gamma [feat], grad_beta [feat])"""
+    _chk(grad_y)
+    rows, feat = x.shape
+    L = _lib.load()
+    gx = torch.empty_like(x)
+    gg = torch.empty(feat, dtype=torch.float32, device=x.device)
+    gb = torch.empty(feat, dtype=torch.float32, device=x.device)
+    if rows == 0:
+        return gx, gg.zero_(), gb.zero_()
+    partial = torch.empty(L.i3d_ln_res_partial_floats(rows, feat), dtype=torch.float32, device=x.device)
+    check(L.i3d_ln_res_bwd(_p(grad_y), _p(x), _p(r), _p(gamma), _p(mean), _p(rstd), rows, feat, _p(gx), _p(partial), _p(gg),
+                           _p(gb), _stream()), 'i3d_ln_res_bwd')
+    return gx, gg, gb
+
+
+def pair_sum_fwd(u, bias, pidx):
+    """softplus(u_i + u_j + 2 bias) over the pairs of the pair graph index `pidx` -> [pairs, feat] in pair-id order"""
+    _chk(u)
+    _chk(bias)
+    P, feat = pidx.num_edges, u.shape[1]
+    out = torch.empty(P, feat, dtype=torch.float32, device=u.device)
+    check(_lib.load().i3d_pair_sum_fwd(_p(u), _p(bias), _p(pidx.src_s), _p(pidx.dst_s), _p(pidx.perm), P, feat, _p(out),
+                                       _stream()), 'i3d_pair_sum_fwd')
+    return out
+
+
+def pair_sum_bwd(grad_out, u, bias, pidx):
+    """-> grad_u [N, feat]: the per-pair gradients summed per node over both ends (fixed order: segment sums)"""
+    _chk(grad_out)
+    P, feat = pidx.num_edges, u.shape[1]
+    gp = torch.empty(P, feat, dtype=torch.float32, device=u.device)
+    check(_lib.load().i3d_pair_sum_bwd(_p(grad_out), _p(u), _p(bias), _p(pidx.src_s), _p(pidx.dst_s), _p(pidx.perm), P, feat,
+                                       _p(gp), _stream()), 'i3d_pair_sum_bwd')
+    return _pair_node_sums(gp, gp, pidx)
+
+
+def pair_norm_fwd(p, pidx):
+    """||p_i - p_j|| over the pairs of `pidx` -> [pairs, 1] in pair-id order"""
+    _chk(p)
+    P = pidx.num_edges
+    out = torch.empty(P, 1, dtype=torch.float32, device=p.device)
+    check(_lib.load().i3d_pair_norm_fwd(_p(p), _p(pidx.src_s), _p(pidx.dst_s), _p(pidx.perm), P, p.shape[1], _p(out),
+                                        _stream()), 'i3d_pair_norm_fwd')
+    return out
+
+
+def pair_norm_bwd(grad_out, p, dist, pidx):
+    """-> grad_p [N, feat]"""
+    _chk(grad_out)
+    P, feat = pidx.num_edges, p.shape[1]
+    gp = torch.empty(P, 2 * feat, dtype=torch.float32, device=p.device)
+    check(_lib.load().i3d_pair_norm_bwd(_p(grad_out), _p(p), _p(dist), _p(pidx.src_s), _p(pidx.dst_s), _p(pidx.perm), P, feat,
+                                        _p(gp), _stream()), 'i3d_pair_norm_bwd')
+    return _pair_node_sums(gp[:, :feat], gp[:, feat:], pidx)
+
+
+def _pair_node_sums(g_src, g_dst, pidx):
+    """node v: sum of g_src over the pairs that start at v (out_ptr / out_epos) + sum of g_dst over those that end at v (in_ptr);
+    both [pairs, feat] in the pair graph's epos order"""
+    N = pidx.num_nodes
+    out = segment_sum(g_src, pidx.out_ptr, pidx.out_epos, N)
+    return add_inplace(out, segment_sum(g_dst, pidx.in_ptr, None, N))

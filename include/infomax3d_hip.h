@@ -1070,6 +1070,48 @@ int i3d_complete_graph_build(const float* coords, const int* graph_ptr, const in
                              int* inv_perm, int* out_epos, int64_t* src_id, int64_t* dst_id, float* d_id,
                              void* stream);
 
+/* ---- distance-prediction baseline (reference models/distance_predictor.py; csrc/distance.hip) ------------------------
+ * i3d_mha_fwd: the self-attention of torch.nn.TransformerEncoderLayer(batch_first=True) over the atoms of each molecule, the
+ *   molecules given as node ranges [graph_ptr[g], graph_ptr[g+1]) (g < num_graphs) instead of a padded batch with a key
+ *   padding mask (reference distance_predictor.py:50-58).  qkv [N, 3 hidden]: q | k | v rows of the in_proj product (bias
+ *   included), head h at columns h*dh .. h*dh+dh-1 of each third, dh = hidden / nhead <= 128.  out [N, hidden] =
+ *   softmax(scale q k^T) v per (molecule, head), heads concatenated (the input of out_proj); lse [N, nhead] = the row's
+ *   log-sum-exp of scale q k^T, kept for the backward pass.  scale = 1 / sqrt(dh) for torch's attention.
+ * i3d_mha_bwd: grad_qkv [N, 3 hidden] (dQ | dK | dV; every element written) from grad_out [N, hidden] with P recomputed from
+ *   qkv and lse; delta [N, nhead] is scratch (rowsum(grad_out * out) per head).
+ * i3d_ln_res_fwd: y = LayerNorm(x + r) * gamma + beta over rows of `feat` columns (biased variance, eps added inside the
+ *   square root), mean / rstd [rows] saved.
+ * i3d_ln_res_bwd: grad_x [rows, feat] (the gradient of x and of r alike), grad_gamma / grad_beta [feat] as column sums through
+ *   `partial` (i3d_ln_res_partial_floats(rows, feat) floats): per block of rows, then over the blocks in order.
+ * Pair head over the ordered pairs of a pair graph (the complete graph of every molecule: the pairwise_indices of reference
+ * datasets/custom_collate.py:65-78) in its destination-sorted order e: (i, j) = (src_s[e], dst_s[e]), pair id perm[e]:
+ * i3d_pair_sum_fwd: out[perm[e], c] = softplus(u[i, c] + u[j, c] + 2 bias[c]), u [N, feat] (distance_net of one Linear, whose
+ *   two calls on [h_i | h_j] and [h_j | h_i] add up to (W_a + W_b) h_i + (W_a + W_b) h_j + 2 b); out [pairs, feat].
+ * i3d_pair_sum_bwd: grad_pair[e, c] = grad_out[perm[e], c] * sigmoid(u[i, c] + u[j, c] + 2 bias[c]), [pairs, feat], e order.
+ * i3d_pair_norm_fwd: out[perm[e]] = ||p[i] - p[j]||_2, p [N, feat], out [pairs].
+ * i3d_pair_norm_bwd: grad_pair [pairs, 2 feat], e order: columns 0..feat-1 the gradient w.r.t. p[i], columns feat..2 feat-1
+ *   the one w.r.t. p[j]; 0 where the distance is 0.  The per-node sums of grad_pair are i3d_segment_sum over the pair graph's
+ *   out_ptr / out_epos (source side) and in_ptr (destination side). */
+int i3d_mha_fwd(const float* qkv, const int* graph_ptr, int num_graphs, int num_nodes, int hidden, int nhead, float scale,
+                float* out, float* lse, void* stream);
+int i3d_mha_bwd(const float* qkv, const float* out, const float* grad_out, const float* lse, const int* graph_ptr,
+                int num_graphs, int num_nodes, int hidden, int nhead, float scale, float* delta, float* grad_qkv,
+                void* stream);
+int i3d_ln_res_fwd(const float* x, const float* r, const float* gamma, const float* beta, int rows, int feat, float eps,
+                   float* y, float* mean, float* rstd, void* stream);
+long i3d_ln_res_partial_floats(int rows, int feat);
+int i3d_ln_res_bwd(const float* grad_y, const float* x, const float* r, const float* gamma, const float* mean,
+                   const float* rstd, int rows, int feat, float* grad_x, float* partial, float* grad_gamma, float* grad_beta,
+                   void* stream);
+int i3d_pair_sum_fwd(const float* u, const float* bias, const int* src_s, const int* dst_s, const int* perm, int pairs,
+                     int feat, float* out, void* stream);
+int i3d_pair_sum_bwd(const float* grad_out, const float* u, const float* bias, const int* src_s, const int* dst_s,
+                     const int* perm, int pairs, int feat, float* grad_pair, void* stream);
+int i3d_pair_norm_fwd(const float* p, const int* src_s, const int* dst_s, const int* perm, int pairs, int feat, float* out,
+                      void* stream);
+int i3d_pair_norm_bwd(const float* grad_out, const float* p, const float* dist, const int* src_s, const int* dst_s,
+                      const int* perm, int pairs, int feat, float* grad_pair, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
