@@ -30,8 +30,7 @@ _P = c_void_p
 class BnTail(ctypes.Structure):
     _fields_ = [('act', c_int), ('post_act', c_int), ('eps', c_float), ('momentum', c_float), ('gamma', _P),
                 ('beta', _P), ('running_mean', _P), ('running_var', _P), ('mean', _P), ('invstd', _P),
-                ('workspace', _P), ('gemm_workspace', _P), ('gemm_workspace_bytes', c_long), ('num_batches_tracked', _P),
-                ('bias_partial', _P)]
+                ('workspace', _P), ('gemm_workspace', _P), ('gemm_workspace_bytes', c_long), ('num_batches_tracked', _P)]
 
 
 class FcArgs(ctypes.Structure):
@@ -180,7 +179,7 @@ _SIGNATURES = {
     'i3d_gemm_f32_fused_src': (c_int, [c_int, c_int, c_int, _P, c_int, c_long, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int,
                                        _P, _P, _P, c_long, _P]),
     'i3d_pna_pack_h_weights': (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
-    'i3d_bn_bwd_strided': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    'i3d_bn_bwd_strided': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     'i3d_wgrad_multi_supported': (c_int, [POINTER(WgradProblem), c_int, POINTER(WgradOutput), c_int]),
     'i3d_wgrad_multi_workspace_bytes': (c_long, [c_int]),
     'i3d_wgrad_multi_min_workspace_bytes': (c_long, [POINTER(WgradProblem), c_int]),
@@ -232,7 +231,7 @@ _SIGNATURES = {
     'i3d_pna_aggregate_fwd_ex': (c_int, [_P, c_int, _P, _P, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_float, _P, _P]),
     'i3d_pna_aggregate_bwd_ex': (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_float, _P, _P]),
     'i3d_gemm_f32_fused_bf16out': (c_int, [c_int, c_int, c_int, _P, c_int, c_long, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
-    'i3d_bn_bwd_x_bf16': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'i3d_bn_bwd_x_bf16': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'i3d_pna_aggregate_bwd_aff': (c_int, [_P, _P, _P, _P, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int,
                                           c_float, _P, _P]),
     'i3d_bn_bias_partial_floats': (c_long, [c_int]),
@@ -244,9 +243,6 @@ _SIGNATURES = {
     'i3d_panel_stats_tiles': (c_int, [c_int]),
     'i3d_panel_gemm_fused': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P]),
     'i3d_bn_bwd_one_launch_supported': (c_int, [c_int, c_int]),
-    'i3d_bn_bwd_deferred_bias': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_long,
-                                         _P, _P, _P]),
-    'i3d_bn_bias_finalize': (c_int, [_P, c_int, c_int, _P, _P]),
     'i3d_bn_bwd_edge_sums': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P]),
     'i3d_colsum_strided': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     'i3d_wgrad_stream_join': (c_int, [_P]),

@@ -1080,9 +1080,6 @@ static bool fused_final() {
     return on;
 }
 
-// the bias gradient of a Linear directly in front of a BatchNorm (no activation) is written as the exact value, zero (see bn_bwd_impl)
-static bool exact_zero_bias_grad() { return true; }
-
 static float* partial_of(void* workspace) { return (float*)((char*)workspace + WS_HEADER); }
 
 // [3 feat] doubles per rank in a mailbox slot, one flag per column block
@@ -1115,15 +1112,20 @@ static long two_pass_workspace_bytes(int feat) {
     return WS_HEADER + (long)MAX_PARTIAL_BLOCKS * 2 * feat * sizeof(float) + 4 * (long)feat * sizeof(double) + 64;
 }
 
+// the shapes bn_bwd_fused_kernel takes: float4 columns, its LDS sums, and every workgroup resident (the residency argument above)
+static bool one_launch_shape(int rows, int feat) {
+    return rows > 0 && feat > 0 && feat % 4 == 0 && feat <= 2048 &&
+           (long)rows <= (long)FUSED_MAX_BLOCKS * (FUSED_THREADS / (feat / 4)) * FUSED_MAX_RPT;
+}
+
 // launches bn_bwd_fused_kernel when the call qualifies (-> true)
 static bool bn_bwd_one_launch(const BwdApplyArgs& b, int rows, int feat, void* workspace, float* grad_beta, float* grad_gamma, hipStream_t s) {
-    if (!g_one_launch || !fused_final() || feat % 4 != 0 || feat > 2048 || b.pre != nullptr || b.grad_pre == nullptr) return false;
+    if (!g_one_launch || !fused_final() || !one_launch_shape(rows, feat) || b.pre != nullptr || b.grad_pre == nullptr) return false;
     if (b.ld_out % 4 != 0 || ((((uintptr_t)b.grad_y) | ((uintptr_t)b.grad_pre)) & 15) != 0 || (((uintptr_t)b.x) & (b.x_bf16 ? 7 : 15)) != 0)
         return false;
     FusedBwdGeom ge;
     ge.tpr = feat / 4;
     ge.rl = FUSED_THREADS / ge.tpr;
-    if ((long)rows > (long)FUSED_MAX_BLOCKS * ge.rl * FUSED_MAX_RPT) return false;       // (the residency argument above)
     int G = cdiv(rows, ge.rl);
     if (G > FUSED_MAX_BLOCKS) G = FUSED_MAX_BLOCKS;
     ge.rpb = cdiv(rows, G);
@@ -1306,18 +1308,9 @@ static void launch_bwd_apply(BwdApplyArgs& g, int rows, int feat, hipStream_t s)
     }
 }
 
-extern "C" int i3d_bn_bwd(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act,
-                          int post_act, const float* mean, const float* invstd, const float* gamma,
-                          const float* beta, float* grad_gamma, float* grad_beta, float* grad_pre, float* grad_bias,
-                          double* sums_out, const double* sums_in, long total_rows, void* workspace, void* stream) {
-    return i3d_bn_bwd_deferred_bias(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
-                                    grad_pre, grad_bias, sums_out, sums_in, total_rows, workspace, nullptr, stream);
-}
-
 // would i3d_bn_bwd (activation none / ReLU / LeakyReLU, fp32 x, no bias column sums) take the one-launch kernel for this shape?
 extern "C" int i3d_bn_bwd_one_launch_supported(int rows, int feat) {
-    if (!g_one_launch || !fused_final() || collectives() != nullptr || feat % 4 != 0 || feat > 2048 || rows <= 0) return 0;
-    return (long)rows <= (long)FUSED_MAX_BLOCKS * (FUSED_THREADS / (feat / 4)) * FUSED_MAX_RPT ? 1 : 0;
+    return g_one_launch && fused_final() && collectives() == nullptr && one_launch_shape(rows, feat) ? 1 : 0;
 }
 
 extern "C" int i3d_set_bn_bwd_one_launch(int on) {
@@ -1328,19 +1321,6 @@ extern "C" int i3d_set_bn_bwd_one_launch(int on) {
 
 extern "C" long i3d_bn_bias_partial_floats(int feat) { return (long)MAX_PARTIAL_BLOCKS * 2 * feat; }
 
-// grad_bias = column sums of grad_pre from the row-chunk partials the data-gradient pass left in bias_partial
-extern "C" int i3d_bn_bias_finalize(const float* bias_partial, int rows, int feat, float* grad_bias, void* stream) {
-    I3D_CHECK_ARG(bias_partial != nullptr && rows > 0 && feat > 0 && grad_bias != nullptr, "bad arguments");
-    const Chunking ch = make_chunking(rows, feat);
-    hipLaunchKernelGGL(pair_final_kernel, dim3(cdiv(feat, FIN_COLS)), dim3(256), 0, (hipStream_t)stream, bias_partial, ch.nblk,
-                       feat, grad_bias, (float*)nullptr, (double*)nullptr);
-    I3D_CHECK_LAUNCH();
-    return I3D_OK;
-}
-
-// bias_partial != null (and grad_bias != null): the data-gradient pass stores the row-chunk partials of the bias gradient
-// there and does NOT finalise them - the in-launch finalisation is a ~10 us serial tail on the backward chain for a value
-// only the optimizer needs; the caller runs i3d_bn_bias_finalize later (the layer composite: on its side stream).
 // the BatchNorm input x of the next bn_bwd_impl calls of this thread is stored as bf16 (i3d_bn_bwd_x_bf16)
 static thread_local int g_x_bf16 = 0;
 // the data-gradient pass of the next bn_bwd_impl call of this thread is bn_bwd_apply_edge_sums_kernel (i3d_bn_bwd_edge_sums)
@@ -1352,7 +1332,7 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
                        int post_act, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, float* grad_gamma, float* grad_beta, float* grad_pre,
                        float* grad_bias, double* sums_out, const double* sums_in, long total_rows,
-                       void* workspace, float* bias_partial, int ld_out, void* stream) {
+                       void* workspace, int ld_out, void* stream) {
     I3D_CHECK_ARG(rows > 0 && feat > 0, "rows > 0 and feat > 0 required");
     I3D_CHECK_ARG(workspace != nullptr, "workspace required");
     I3D_CHECK_ARG(act == I3D_ACT_NONE || act == I3D_ACT_RELU || act == I3D_ACT_LEAKY_RELU || pre != nullptr, "pre required for this activation");
@@ -1381,14 +1361,14 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
             g_sums_ready = 1;
             const int rc = bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
                                        grad_pre, grad_bias, nullptr, (const double*)tmp /* non-null: phase 2 */, 0, workspace,
-                                       bias_partial, ld_out, stream);
+                                       ld_out, stream);
             g_sums_ready = 0;
             return rc;
         }
         I3D_CHECK_ARG((pc ? peer_scratch_bytes(pc) : coll->scratch_bytes) >= (long)(2 * feat + 1) * 8, "collective scratch too small");
         double* s64 = (double*)(pc ? peer_scratch(pc) : coll->scratch);
         int rc = bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
-                             nullptr, nullptr, s64, nullptr, rows, workspace, nullptr, ld_out, stream);
+                             nullptr, nullptr, s64, nullptr, rows, workspace, ld_out, stream);
         if (rc != I3D_OK) return rc;
         if (pc != nullptr) {
             // peer-write exchange (peer.h): row count appended, sums over the ranks, conversion to the fp32 vectors + 1 / rows
@@ -1398,7 +1378,7 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
             if (rc != I3D_OK) return rc;
             g_sums_ready = 1;
             rc = bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
-                             grad_pre, grad_bias, nullptr, s64, 0, workspace, bias_partial, ld_out, stream);
+                             grad_pre, grad_bias, nullptr, s64, 0, workspace, ld_out, stream);
             g_sums_ready = 0;
             return rc;
         }
@@ -1407,12 +1387,12 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
         rc = coll->all_reduce_f64(coll->user, s64, 2 * feat + 1, stream);
         if (rc != I3D_OK) return rc;
         return bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
-                           grad_pre, grad_bias, nullptr, s64, 0, workspace, bias_partial, ld_out, stream);
+                           grad_pre, grad_bias, nullptr, s64, 0, workspace, ld_out, stream);
     }
     Chunking ch = make_chunking(rows, feat);
     float* partial = partial_of(workspace);
     if (sums_in == nullptr && sums_out == nullptr && g_edge_sums == nullptr && grad_pre != nullptr &&
-        (grad_bias == nullptr || (act == I3D_ACT_NONE && exact_zero_bias_grad()))) {
+        (grad_bias == nullptr || act == I3D_ACT_NONE)) {
         // one launch: reduction, finalisation and data gradient (bn_bwd_fused_kernel) - tensors of up to 256 * rl * 4 rows
         BwdApplyArgs b = {};
         b.grad_y = grad_y; b.x = x; b.pre = relu_class(act) ? nullptr : pre; b.mean = mean; b.invstd = invstd; b.gamma = gamma;
@@ -1458,7 +1438,7 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
         I3D_CHECK_LAUNCH();
         return I3D_OK;
     }
-    if (grad_bias != nullptr && act == I3D_ACT_NONE && exact_zero_bias_grad()) {
+    if (grad_bias != nullptr && act == I3D_ACT_NONE) {
         // No activation between the Linear and the BatchNorm: the bias gradient is the column sum of the BatchNorm input
         // gradient  s (dy - mean(dy) - xhat mean(dy xhat))  over the rows the statistics were taken over, which is
         // IDENTICALLY zero (sum xhat = 0).  The reference sums it up in fp32 and gets rounding noise (~1e-9 of the scale,
@@ -1475,21 +1455,15 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
         b.items = 0;
         dim3 grid(ch.nblk, ch.ncolblk);
         Final f = pair_final_desc(workspace, feat, grad_bias, nullptr, nullptr);
-        float* bias_part = partial;
-        if (bias_partial != nullptr) {       // deferred: partials to the caller's buffer, no finalisation here
-            f.counters = nullptr;
-            bias_part = bias_partial;
-        }
         const bool ga = !(relu_class(b.act) && relu_class(b.post_act));
         if (ch.V == 4) {
-            if (ga) hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<4, true>), grid, dim3(256), 0, s, b, ch, rows, bias_part, f);
-            else hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<4, false>), grid, dim3(256), 0, s, b, ch, rows, bias_part, f);
+            if (ga) hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<4, true>), grid, dim3(256), 0, s, b, ch, rows, partial, f);
+            else hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<4, false>), grid, dim3(256), 0, s, b, ch, rows, partial, f);
         } else {
-            if (ga) hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<1, true>), grid, dim3(256), 0, s, b, ch, rows, bias_part, f);
-            else hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<1, false>), grid, dim3(256), 0, s, b, ch, rows, bias_part, f);
+            if (ga) hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<1, true>), grid, dim3(256), 0, s, b, ch, rows, partial, f);
+            else hipLaunchKernelGGL((bn_bwd_apply_colsum_kernel<1, false>), grid, dim3(256), 0, s, b, ch, rows, partial, f);
         }
         I3D_CHECK_LAUNCH();
-        if (bias_partial != nullptr) return I3D_OK;
         if (f.counters == nullptr) {
             hipLaunchKernelGGL(pair_final_kernel, dim3(cdiv(feat, FIN_COLS)), dim3(256), 0, s, partial, ch.nblk, feat, grad_bias,
                                (float*)nullptr, (double*)nullptr);
@@ -1502,13 +1476,12 @@ static int bn_bwd_impl(const float* grad_y, const float* x, const float* pre, in
     return I3D_OK;
 }
 
-extern "C" int i3d_bn_bwd_deferred_bias(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act,
-                                        int post_act, const float* mean, const float* invstd, const float* gamma,
-                                        const float* beta, float* grad_gamma, float* grad_beta, float* grad_pre,
-                                        float* grad_bias, double* sums_out, const double* sums_in, long total_rows,
-                                        void* workspace, float* bias_partial, void* stream) {
+extern "C" int i3d_bn_bwd(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act,
+                          int post_act, const float* mean, const float* invstd, const float* gamma,
+                          const float* beta, float* grad_gamma, float* grad_beta, float* grad_pre, float* grad_bias,
+                          double* sums_out, const double* sums_in, long total_rows, void* workspace, void* stream) {
     return bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta, grad_pre,
-                       grad_bias, sums_out, sums_in, total_rows, workspace, bias_partial, feat, stream);
+                       grad_bias, sums_out, sums_in, total_rows, workspace, feat, stream);
 }
 
 extern "C" int i3d_bn_bwd_edge_sums(const float* grad_y, const float* x, int rows, int feat, int act, const float* mean,
@@ -1524,7 +1497,7 @@ extern "C" int i3d_bn_bwd_edge_sums(const float* grad_y, const float* x, int row
     const EdgeSums es{in_ptr, out_ptr, out_epos, num_nodes, out_src, out_dst, ldo};
     g_edge_sums = &es;
     const int rc = bn_bwd_impl(grad_y, x, nullptr, rows, feat, act, I3D_ACT_NONE, mean, invstd, gamma, beta, grad_gamma, grad_beta, grad_pre,
-                               nullptr, nullptr, nullptr, rows, workspace, nullptr, feat, stream);
+                               nullptr, nullptr, nullptr, rows, workspace, feat, stream);
     g_edge_sums = nullptr;
     return rc;
 }
@@ -1546,16 +1519,16 @@ extern "C" int i3d_colsum_strided(const float* x, int ldx, int rows, int feat, f
     return I3D_OK;
 }
 
-// i3d_bn_bwd_deferred_bias with the BatchNorm input x stored as bf16 (row r at (bf16*)x + r * feat; feat % 4 == 0; activations
+// i3d_bn_bwd with the BatchNorm input x stored as bf16 (row r at (bf16*)x + r * feat; feat % 4 == 0; activations
 // none / ReLU / LeakyReLU: act' is taken from x): the bf16 mode's storage form of a PNA layer's messages
 extern "C" int i3d_bn_bwd_x_bf16(const float* grad_y, const void* x, int rows, int feat, int act, int post_act, const float* mean,
                                  const float* invstd, const float* gamma, const float* beta, float* grad_gamma, float* grad_beta,
-                                 float* grad_pre, float* grad_bias, void* workspace, float* bias_partial, void* stream) {
+                                 float* grad_pre, float* grad_bias, void* workspace, void* stream) {
     I3D_CHECK_ARG(feat % 4 == 0 && (((uintptr_t)x) & 7) == 0, "bf16 x: feat % 4 == 0, 8-byte aligned");
     I3D_CHECK_ARG(act == I3D_ACT_NONE || act == I3D_ACT_RELU || act == I3D_ACT_LEAKY_RELU, "bf16 x: act' must not need the Linear output");
     g_x_bf16 = 1;
     const int rc = bn_bwd_impl(grad_y, (const float*)x, nullptr, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta,
-                               grad_pre, grad_bias, nullptr, nullptr, rows, workspace, bias_partial, feat, stream);
+                               grad_pre, grad_bias, nullptr, nullptr, rows, workspace, feat, stream);
     g_x_bf16 = 0;
     return rc;
 }
@@ -1564,10 +1537,10 @@ extern "C" int i3d_bn_bwd_x_bf16(const float* grad_y, const void* x, int rows, i
 extern "C" int i3d_bn_bwd_strided(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act,
                                   int post_act, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                   float* grad_gamma, float* grad_beta, float* grad_pre, int ld_out, float* grad_bias,
-                                  void* workspace, float* bias_partial, void* stream) {
+                                  void* workspace, void* stream) {
     I3D_CHECK_ARG(ld_out >= feat && (feat % 4 != 0 || (ld_out % 4 == 0 && (((uintptr_t)grad_pre) & 15) == 0)), "bad output pitch");
     return bn_bwd_impl(grad_y, x, pre, rows, feat, act, post_act, mean, invstd, gamma, beta, grad_gamma, grad_beta, grad_pre,
-                       grad_bias, nullptr, nullptr, rows, workspace, bias_partial, ld_out, stream);
+                       grad_bias, nullptr, nullptr, rows, workspace, ld_out, stream);
 }
 
 extern "C" int i3d_bn_eval_bwd(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act,

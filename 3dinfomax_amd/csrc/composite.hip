@@ -114,15 +114,8 @@ static int tail_fwd(const I3dBnTail* t, int rows, int f_out, float* pre, float* 
 // BN/activation backward; grad_bias = column sums of grad_pre from the same pass
 static int tail_bwd(const I3dBnTail* t, int rows, int f_out, const float* grad_y, const float* xact, const float* pre,
                     float* grad_gamma, float* grad_beta, float* grad_pre, float* grad_bias, void* stream) {
-    return i3d_bn_bwd_deferred_bias(grad_y, xact, pre, rows, f_out, t->act, t->post_act, t->mean, t->invstd, t->gamma, t->beta,
-                                    grad_gamma, grad_beta, grad_pre, grad_bias, nullptr, nullptr, rows, t->workspace,
-                                    t->bias_partial, stream);
-}
-
-// the deferred half of tail_bwd: first thing on the stream the block's weight gradients run on
-static int bias_final(const I3dBnTail* t, int rows, int f_out, float* grad_bias, void* wst) {
-    if (t->bias_partial == nullptr || grad_bias == nullptr) return I3D_OK;
-    return i3d_bn_bias_finalize(t->bias_partial, rows, f_out, grad_bias, wst);
+    return i3d_bn_bwd(grad_y, xact, pre, rows, f_out, t->act, t->post_act, t->mean, t->invstd, t->gamma, t->beta, grad_gamma,
+                      grad_beta, grad_pre, grad_bias, nullptr, nullptr, rows, t->workspace, stream);
 }
 
 // ---- plain FC ------------------------------------------------------------------------------------------
@@ -137,28 +130,14 @@ extern "C" int i3d_fc_bn_fwd(const I3dFcArgs* a, void* stream) {
 // waits for) on `stream`, and the weight gradients, which only need the block's grad_pre, on `wst` - the same stream for
 // the stand-alone entry points, the side stream for a PNA layer (which issues the weight gradients of several blocks behind
 // ONE fork: a fork or join costs the host ~7 us, tools/probes/forkjoin_probe.hip).
-// the bias gradient of a block next to its weight gradients (on their stream)
-// A block with an activation in front of its BatchNorm: the bias gradient is the column sum of grad_pre.  Where the one-launch
-// BatchNorm backward takes the shape (bn.hip), the chain runs it WITHOUT those sums (reduction + data gradient + their column sums
-// were two launches: 10 + 11.5 us at the head's 512 rows) and the sums are taken next to the weight gradients, from grad_pre.
-static bool bias_aside(const I3dFcArgs* a, int xact_bf16 = 0) {
-    return !xact_bf16 && a->grad_bias != nullptr && a->tail.bias_partial != nullptr && a->tail.act != I3D_ACT_NONE && relu_class(a->tail.act) &&
-           relu_class(a->tail.post_act) && a->pre_keep == nullptr && i3d_bn_bwd_one_launch_supported(a->rows, a->f_out) != 0;
-}
-
-static int bias_final_fc(const I3dFcArgs* a, void* wst, int xact_bf16 = 0) {
-    if (bias_aside(a, xact_bf16)) return i3d_colsum_strided(a->grad_pre, a->f_out, a->rows, a->f_out, a->grad_bias, a->tail.bias_partial, wst);
-    return bias_final(&a->tail, a->rows, a->f_out, a->grad_bias, wst);
-}
-
 static int fc_bn_bwd_chain(const I3dFcArgs* a, void* stream, int xact_bf16 = 0) {
     if (xact_bf16)      // the block's activation (a PNA layer's messages) is stored as bf16
         TRY(i3d_bn_bwd_x_bf16(a->grad_y, a->xact, a->rows, a->f_out, a->tail.act, a->tail.post_act, a->tail.mean, a->tail.invstd,
-                              a->tail.gamma, a->tail.beta, a->grad_gamma, a->grad_beta, a->grad_pre, a->grad_bias, a->tail.workspace,
-                              a->tail.bias_partial, stream));
+                              a->tail.gamma, a->tail.beta, a->grad_gamma, a->grad_beta, a->grad_pre, a->grad_bias,
+                              a->tail.workspace, stream));
     else
         TRY(tail_bwd(&a->tail, a->rows, a->f_out, a->grad_y, a->xact, a->pre_keep, a->grad_gamma, a->grad_beta, a->grad_pre,
-                     bias_aside(a, xact_bf16) ? nullptr : a->grad_bias, stream));
+                     a->grad_bias, stream));
     if (a->grad_x != nullptr) {
         if (panel_ok(a->W_dgrad_panel, a->f_out, a->f_in) && (((uintptr_t)a->grad_pre | (uintptr_t)a->grad_x) & 15) == 0)
             TRY(i3d_panel_gemm(a->rows, a->f_in, a->f_out, a->grad_pre, a->f_out, a->W_dgrad_panel, a->grad_x, a->f_in, nullptr, 0, stream));
@@ -172,7 +151,6 @@ static int fc_bn_bwd_chain(const I3dFcArgs* a, void* stream, int xact_bf16 = 0) 
 // x_aff != null (fused BatchNorm): a->x is the RAW activation of the block in front, its BatchNorm output
 // (x - mean) * scale + shift was never materialised; the product is corrected in the slice reduction (gemm.hip)
 static int fc_bn_bwd_wgrad(const I3dFcArgs* a, void* wst, const float* x_aff = nullptr) {
-    TRY(bias_final_fc(a, wst));
     if (x_aff != nullptr)
         return i3d_gemm_f32_wgrad_bn(a->f_out, a->f_in, a->rows, a->grad_pre, a->f_out, a->x, a->f_in, a->grad_W, a->ldw,
                                      a->grad_bias, x_aff, a->tail.gemm_workspace, a->tail.gemm_workspace_bytes, wst);
@@ -255,7 +233,6 @@ static int edge_fc_bn_bwd_wgrad_p(const I3dEdgeFcArgs* a, void* wst) {
 // grad_pre only.
 static int edge_fc_bn_bwd_wgrad_q(const I3dEdgeFcArgs* a, void* wst) {
     const int Fh = a->f_h, Fo = a->f_out, E = a->num_edges;
-    TRY(bias_final(&a->tail, E, Fo, a->grad_bias, wst));
     void* ws = a->tail.gemm_workspace;
     const long wsb = a->tail.gemm_workspace_bytes;
     if (a->q != nullptr && a->q_rows > 0) {
@@ -310,7 +287,6 @@ static int grouped_fc_bn_bwd_chain(const I3dGroupedFcArgs* a, void* stream, int 
 
 static int grouped_fc_bn_bwd_wgrad(const I3dGroupedFcArgs* a, void* wst) {
     const int Fh = a->f_h, Fo = a->f_out, A = a->agg_width, N = a->num_nodes;
-    TRY(bias_final(&a->tail, N, Fo, a->grad_bias, wst));
     TRY(i3d_gemm_f32_ws(1, 0, Fo, Fh, N, a->grad_pre, Fo, a->h, Fh, a->grad_W, a->ldw, nullptr, 0, a->tail.gemm_workspace,
                         a->tail.gemm_workspace_bytes, wst));
     // dW_D = dY_D^T a_D over the rows of each in-degree group, all groups in one launch
@@ -460,17 +436,10 @@ static int pna_layer_wgrad_multi(const I3dPnaLayerArgs* a, void* wst, bool dry_r
     const long wsb = e->tail.gemm_workspace_bytes;
     if (ws == nullptr || !i3d_wgrad_multi_supported(pr, np, out, no) || i3d_wgrad_multi_min_workspace_bytes(pr, np) > wsb) return 0;
     if (dry_run) return 1;                             // the layer is covered
-    if (do_post) TRY(bias_final(&g->tail, N, g->f_out, g->grad_bias, wst));
-    for (int i = a->n_pre_extra - 1; i >= 0 && do_pre; --i)
-        TRY(bias_final_fc(&a->pre[i], wst, (a->fused_bn && a->msg_bf16 && i == a->n_pre_extra - 1) ? 1 : 0));
-    if (do_pre) {
-        if (edge_bwd_fused_ok(a) && edge_bias_on_chain(a)) {
-            // (taken on the caller's stream at the end of the layer's backward: see there)
-        } else if (edge_bwd_fused_ok(a))      // the bias gradient = column sum of dP[dst] (the layer's backward took i3d_bn_bwd_edge_sums)
-            TRY(i3d_colsum_strided(a->DL + Fo, 2 * Fo + a->post.f_out, N, Fo, e->grad_bias, a->edge_bias_partial, wst));
-        else
-            TRY(bias_final(&e->tail, E, Fo, e->grad_bias, wst));
-    }
+    // the fused edge backward leaves the bias gradient = column sum of dP[dst] to its caller: here, unless the layer's backward
+    // takes it on its own stream at its end (edge_bias_on_chain)
+    if (do_pre && edge_bwd_fused_ok(a) && !edge_bias_on_chain(a))
+        TRY(i3d_colsum_strided(a->DL + Fo, 2 * Fo + a->post.f_out, N, Fo, e->grad_bias, a->edge_bias_partial, wst));
     TRY(i3d_wgrad_multi(pr, np, out, no, ws, wsb, wst));
     if (!do_pre) return 1;
     const int V = e->q_rows;
@@ -656,7 +625,7 @@ extern "C" int i3d_pna_layer_bwd(const I3dPnaLayerArgs* a, void* stream) {
         float* dlin = a->DL + 2 * a->edge.f_out;
         TRY(i3d_bn_bwd_strided(g->grad_y, g->xact, g->pre_keep, g->num_nodes, g->f_out, g->tail.act, g->tail.post_act, g->tail.mean,
                                g->tail.invstd, g->tail.gamma, g->tail.beta, g->grad_gamma, g->grad_beta, dlin, WLb, g->grad_bias,
-                               g->tail.workspace, g->tail.bias_partial, stream));
+                               g->tail.workspace, stream));
         TRY(i3d_gemm_f32_grouped(0, g->m_padded, g->agg_width, g->f_out, dlin, WLb, g->num_nodes, g->deg_rows, g->deg_tile_group, g->WD,
                                  g->agg_width, (long)g->f_out * g->agg_width, g->grad_agg, g->agg_width, 0, stream));
     } else {
@@ -691,10 +660,11 @@ extern "C" int i3d_pna_layer_bwd(const I3dPnaLayerArgs* a, void* stream) {
         // round 6: where the one-launch BatchNorm backward takes the shape (bn.hip: bn_bwd_fused_kernel, 16-17 us at batch 512) it
         // writes g and the pair of segmented sums follows (8.5 us) - against reduction 15.5 us + i3d_bn_bwd_edge_sums 17-20 us.
         // (profiles/r06_ab_edge_onelaunch.txt: 1.951 -> 1.925 ms)
+        // (a supported shape with pointers off 16-byte alignment is still correct: i3d_bn_bwd_strided falls through to the two passes)
         if (i3d_bn_bwd_one_launch_supported(e->num_edges, e->f_out)) {
             TRY(i3d_bn_bwd_strided(e->grad_y, e->xact, nullptr, e->num_edges, e->f_out, e->tail.act, I3D_ACT_NONE, e->tail.mean, e->tail.invstd,
                                    e->tail.gamma, e->tail.beta, e->grad_gamma, e->grad_beta, e->grad_pre, e->f_out, nullptr,
-                                   e->tail.workspace, nullptr, stream));
+                                   e->tail.workspace, stream));
             TRY(i3d_segment_sum_pair(e->grad_pre, e->f_out, e->out_ptr, e->out_epos, a->DL, e->in_ptr, nullptr, a->DL + e->f_out,
                                      e->num_nodes, e->f_out, WLb, stream));
         } else

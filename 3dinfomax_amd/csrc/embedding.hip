@@ -138,7 +138,7 @@ embedding_sum_bwd_lds_kernel(const int64_t* __restrict__ idx, const int* __restr
 
 using namespace i3d;
 
-extern "C" int i3d_abi_version(void) { return 1; }
+extern "C" int i3d_abi_version(void) { return 2; }
 
 extern "C" const char* i3d_last_error(void) { return g_err; }
 

@@ -861,9 +861,6 @@ static void launch_slab_reduce(const SlabReduce& a, hipStream_t s) {
 static bool narrow_pays(int N, long tiles64) {
     return tiles64 < 1100 && (long)cdiv(N, 64) * 64 * 10 > (long)cdiv(N, 32) * 32 * 11;
 }
-// the fused (BatchNorm prologue / statistics epilogue) forward GEMM at K < 400 keeps 64x64 tiles: measured 2.464 ms per
-// step with the narrow tiling against 2.426 ms without (tools/ab.sh, 4 interleaved runs) (left off)
-static bool fuse_narrow_short_k() { return false; }
 
 // process-level: 0 = fp32 MFMA (exact fp32 products), 1 = bf16 MFMA on bf16-rounded operands (i3d_set_matmul_precision)
 static int g_matmul_bf16 = 0;
@@ -1517,8 +1514,9 @@ extern "C" int i3d_gemm_f32_fused_src(int M, int N, int K, const float* A, int l
     if (rc != I3D_OK) return rc;
     const int fuse = (a_aff != nullptr ? 1 : 0) | (stats != nullptr ? 2 : 0);
     hipStream_t s = (hipStream_t)stream;
-    // tile choice as in gemm_impl for the forward layout: 64x64 (idx-major image), 64x32 when K is long and N pads badly
-    const bool narrow = narrow_pays(N, (long)cdiv(M, 64) * cdiv(N, 64)) && (K >= 400 || fuse_narrow_short_k());
+    // tile choice as in gemm_impl for the forward layout: 64x64 (idx-major image), 64x32 when K is long and N pads badly (at
+    // K < 400 the narrow tiling measured slower: 2.464 against 2.426 ms per step, tools/ab.sh, 4 interleaved runs)
+    const bool narrow = narrow_pays(N, (long)cdiv(M, 64) * cdiv(N, 64)) && K >= 400;
     if (g_matmul_bf16 && bf16_bk() == 32) {
         if (narrow) launch_fused<Cfg14>(g, fuse, s);
         else launch_fused<Cfg13>(g, fuse, s);

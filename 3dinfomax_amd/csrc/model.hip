@@ -72,11 +72,6 @@ struct PnaCtx {
     int gh_cur = 0;                 // which of the two dL/dh buffers holds the gradient after the layers done so far (backward)
 };
 
-// (measured and left off: the bias gradients are finalised from row-chunk partials on the weight-gradient stream instead of
-// inside the data-gradient pass (I3dBnTail.bias_partial).  Off by default: measured on one box (tools/ab.sh, 4 interleaved
-// runs of 300 steps) 2.816 ms deferred against 2.787 ms in-launch - it takes ~10 us per BatchNorm off the main stream's
-// chain but adds three small launches per layer to the side stream, whose join is what the next layer waits for: at batch
-// 512 the backward pass is bound by the TOTAL work of the two streams, not by the chain.
 // the [rows, v] multi-hot matrices of the atom / bond-combination features (columns: the concatenated vocabularies, padded
 // to 32): embedding-table gradients are their transposes times dL/d(embedding)
 int encoder_multihot(const PnaCtx& c, float* hot_atoms, float* hot_bonds, void* stream) {
@@ -90,31 +85,6 @@ int encoder_multihot(const PnaCtx& c, float* hot_atoms, float* hot_bonds, void* 
     return i3d_multihot(b.comb, nullptr, b.n_comb, m.n_bond_tables, offs, (o + 31) / 32 * 32, hot_bonds, stream);
 }
 
-bool hoist_weights() {
-    return true;
-}
-
-bool defer_bias() {
-    return false;
-}
-
-// I3D_WGRAD_JOIN=layer: the backward pass of every layer waits for its weight gradients (round-1 behaviour).  Default
-// `model`: one join at the end of the model's backward - the weight-gradient stream turned out to be the critical path
-// of a layer (~214 us of GEMMs per layer behind the first fork against ~150 us left on the chain), a join per layer
-// makes the chain of the NEXT layer wait for it.  Costs scratch: what that stream reads or writes is kept per layer.
-bool join_per_layer() {
-    return false;      // (one join per model backward: per-layer joins measured slower, docs/history)
-}
-
-// The first layer's weight gradients (the last ones of a backward pass, and what the step waits for at its very end) as two
-// launches, the posttrans products early, next to that layer's chain: only the pretrans / bond-table products are left when the
-// chain ends.  Before the chain's kernels had wave priority this lost (2.289 against 2.253 ms: the early launch took the CUs from
-// the chain it was meant to hide behind); with it: 2.141 against 2.152 ms (tools/ab.sh, 5 interleaved runs).  Every layer split
-// the same way (every layer) loses 40 us: one more launch + reduction per layer for work that was hidden anyway.
-int split_wgrad() {     // 0: no layer, 1: the first layer (last of the backward pass), 2: every layer
-    return 1;
-}
-
 // bf16 matmul mode: a layer's messages ([E, F], the last pretrans block's activation) stored as bf16 once they are large enough to
 // be bound by their bytes (I3D_MSG_BF16=0: never, =force: at every size; default: E * F * 4 >= 32 MB - the QMugs shape, not the QM9 one)
 bool msg_bf16_storage(const I3dPnaModel& m, long E) {
@@ -123,12 +93,6 @@ bool msg_bf16_storage(const I3dPnaModel& m, long E) {
     if (e != nullptr && e[0] == '0') return false;
     if (e != nullptr && e[0] == 'f') return true;
     return E * (long)m.hidden * 4 >= (32L << 20);
-}
-
-// I3D_MERGE_H=0: the products that read the node features (edge block's P, posttrans block's h-term, and their data gradients)
-// as separate GEMMs (round 2) instead of one per direction
-bool merge_h() {
-    return true;
 }
 
 bool simple_act(int act) { return act == I3D_ACT_NONE || act == I3D_ACT_RELU || act == I3D_ACT_LEAKY_RELU; }
@@ -148,7 +112,6 @@ void fill_tail(I3dBnTail& t, const I3dFcParams& p, float* mean, float* invstd) {
     t.workspace = nullptr;
     t.gemm_workspace = nullptr;
     t.gemm_workspace_bytes = 0;
-    t.bias_partial = nullptr;
 }
 
 void set_ws(I3dBnTail& t, void* bn_ws, void* gemm_ws, long gemm_ws_bytes) {
@@ -190,9 +153,9 @@ long head_colsum_floats(const I3dPnaModel& m, long B) {
 long side_floats(const I3dPnaModel& m, const I3dPnaBatch& b, int l) {
     const long N = b.num_nodes, E = b.num_edges, F = m.hidden;
     const long f_msg = m.pre[l][m.n_pre - 1].f_out, A = m.n_aggregators * f_msg, Fo0 = m.pre[l][0].f_out;
-    long t = al4(N * F) + al4((long)b.n_groups * F * A) + al4(i3d_bn_bias_partial_floats((int)F));
-    for (int i = 1; i < m.n_pre; ++i) t += al4(E * (long)m.pre[l][i].f_out) + al4(i3d_bn_bias_partial_floats(m.pre[l][i].f_out));
-    t += al4(E * Fo0) + al4(N * 2 * Fo0) + al4((long)b.v_pad * Fo0) + al4(i3d_bn_bias_partial_floats((int)Fo0));
+    long t = al4(N * F) + al4((long)b.n_groups * F * A);
+    for (int i = 1; i < m.n_pre; ++i) t += al4(E * (long)m.pre[l][i].f_out);
+    t += al4(E * Fo0) + al4(N * 2 * Fo0) + al4((long)b.v_pad * Fo0) + al4(i3d_bn_bias_partial_floats((int)Fo0));      // (edge_bias_partial)
     t += al4(N * (2 * Fo0 + F));        // DL (merged h-products)
     return t;
 }
@@ -245,6 +208,7 @@ long plan_forward(PnaCtx& c, float* saved, float* node_emb, float* out) {
         I3dPnaLayerArgs& a = c.layers[l];
         std::memset(&a, 0, sizeof(a));
         a.fused_bn = 1;
+        a.merge_h = 1;      // the products that read h as ONE GEMM per direction (Wcat / PL below, DL in the backward pass)
         a.stats_ws = stats_ws;
         c.h[l + 1] = (l == L - 1) ? node_emb : ar.take((long)N * F);
         // ---- pretrans block 0: edge gather-combine
@@ -258,14 +222,11 @@ long plan_forward(PnaCtx& c, float* saved, float* node_emb, float* out) {
         e.src_s = b.src_s; e.dst_s = b.dst_s; e.in_ptr = b.in_ptr; e.out_ptr = b.out_ptr; e.out_epos = b.out_epos;
         e.Q = ar.take((long)b.n_comb * Fo0);
         e.P = ar.take((long)N * 2 * Fo0);
-        if (merge_h()) {
-            a.merge_h = 1;
-            a.Wcat = ar.take((long)(2 * Fo0 + F) * F);
-            a.bcat = ar.take(2 * Fo0 + F);
-            a.PL = ar.take((long)N * (2 * Fo0 + F));
-            a.Wcat_panel = ar.take(i3d_panel_packed_bytes(2 * Fo0 + F, F) / 4);      // (csrc/panel.hip; packed where Wcat is)
-            a.Wcat_dgrad_panel = ar.take(i3d_panel_packed_bytes(F, 2 * Fo0 + F) / 4);
-        }
+        a.Wcat = ar.take((long)(2 * Fo0 + F) * F);
+        a.bcat = ar.take(2 * Fo0 + F);
+        a.PL = ar.take((long)N * (2 * Fo0 + F));
+        a.Wcat_panel = ar.take(i3d_panel_packed_bytes(2 * Fo0 + F, F) / 4);      // (csrc/panel.hip; packed where Wcat is)
+        a.Wcat_dgrad_panel = ar.take(i3d_panel_packed_bytes(F, 2 * Fo0 + F) / 4);
         e.xact = ar.take((long)E * Fo0);
         a.aff[0] = ar.take(3L * Fo0);
         const float* x = e.xact;
@@ -278,10 +239,8 @@ long plan_forward(PnaCtx& c, float* saved, float* node_emb, float* out) {
             fc.rows = E; fc.f_in = f_in; fc.f_out = p.f_out; fc.ldw = p.f_in;
             fc.x = x; fc.W = p.W; fc.bias = p.bias;
             fc.xact = ar.take((long)E * p.f_out);
-            if (merge_h()) {
-                fc.W_dgrad_panel = ar.take(i3d_panel_packed_bytes(f_in, p.f_out) / 4);
-                fc.W_fwd_panel = ar.take(i3d_panel_packed_bytes(p.f_out, f_in) / 4);
-            }
+            fc.W_dgrad_panel = ar.take(i3d_panel_packed_bytes(f_in, p.f_out) / 4);
+            fc.W_fwd_panel = ar.take(i3d_panel_packed_bytes(p.f_out, f_in) / 4);
             a.aff[i] = ar.take(3L * p.f_out);
             x = fc.xact;
             f_in = p.f_out;
@@ -360,16 +319,16 @@ extern "C" long i3d_pna_model_saved_floats(const I3dPnaModel* m, const I3dPnaBat
 
 extern "C" long i3d_pna_model_scratch_floats(const I3dPnaModel* m, const I3dPnaBatch* b) {
     if (check_model(m, b) != I3D_OK) return -1;
-    // mirrors the takes of i3d_pna_model_bwd
+    // an upper bound of the takes of i3d_pna_model_bwd: `layer` counts the side stream's buffers of a layer a second time
     const long N = b->num_nodes, E = b->num_edges, B = b->num_graphs, F = m->hidden;
     const long top = 2 * al4(N * F) + al4((long)b->n_comb * F);
     const long head = head_floats(*m, B) + head_colsum_floats(*m, B);
     long layer = 0;
     for (int l = 0; l < m->n_layers; ++l) {
         const long f_msg = m->pre[l][m->n_pre - 1].f_out, A = m->n_aggregators * f_msg, Fo0 = m->pre[l][0].f_out;
-        long t = al4(N * F) + al4((long)b->n_groups * F * A) + al4(N * A) + al4(E * f_msg) + al4(i3d_bn_bias_partial_floats(F));
+        long t = al4(N * F) + al4((long)b->n_groups * F * A) + al4(N * A) + al4(E * f_msg);
         for (int i = 1; i < m->n_pre; ++i)
-            t += al4(E * (long)m->pre[l][i].f_out) + al4(E * (long)m->pre[l][i].f_in) + al4(i3d_bn_bias_partial_floats(m->pre[l][i].f_out));
+            t += al4(E * (long)m->pre[l][i].f_out) + al4(E * (long)m->pre[l][i].f_in);
         t += al4(E * Fo0) + al4(N * 2 * Fo0) + al4(N * F) + al4((long)b->v_pad * Fo0) + al4(i3d_bn_bias_partial_floats(Fo0));
         t += al4(N * (2 * Fo0 + F));
         layer = std::max(layer, t);
@@ -378,7 +337,7 @@ extern "C" long i3d_pna_model_scratch_floats(const I3dPnaModel* m, const I3dPnaB
     for (int k = 0; k < m->n_atom_tables; ++k) oa += m->atom_dims[k];
     for (int k = 0; k < m->n_bond_tables; ++k) ob += m->bond_dims[k];
     const long emb = al4(N * ((oa + 31) / 32 * 32)) + al4((long)b->n_comb * ((ob + 31) / 32 * 32)) + al4(((oa + 3) / 4 * 4) * F);
-    long side = 0;          // generous: the per-layer sets are taken in addition to the shared region
+    long side = 0;
     for (int l = 0; l < m->n_layers; ++l) side += side_floats(*m, *b, l);
     return top + side + head + std::max(layer, emb);
 }
@@ -405,7 +364,7 @@ extern "C" int i3d_pna_model_fwd(const I3dPnaModel* m, const I3dPnaBatch* b, flo
     // bond table) only: those of the layers after the first go to the side stream now (idle in the forward pass) and are
     // awaited before layer 1 - 14 us of small launches per layer off the main chain
     bool hoisted = false;
-    if (L > 1 && hoist_weights()) {
+    if (L > 1) {
         void* side = nullptr;
         TRY(i3d_wgrad_stream_fork(stream, &side));
         if (side != stream) {
@@ -501,16 +460,15 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
     Bump top(scratch);
     float* gh[2] = {top.take((long)N * F), top.take((long)N * F)};      // dL/dh, ping-pong between layers
     float* grad_table = top.take((long)b.n_comb * F);                  // dL/d(bond table), summed over the layers
-    // buffers the weight-gradient stream reads or writes: one set per layer unless every layer joins that stream
-    const bool per_layer_join = join_per_layer();
+    // buffers the weight-gradient stream reads or writes: one set per layer, that stream is joined once, at the end of the model's
+    // backward pass (it is the critical path of a layer: a join per layer made the chain of the NEXT layer wait for it)
     // the last 16 MB of the weight-gradient scratch belong to the launches the MAIN stream issues while the side stream is
     // busy (the atom tables' gradient at the end); the side stream's launches see the front part only
-    const long tail_bytes = (!per_layer_join && gemm_workspace != nullptr && gemm_workspace_bytes >= (64L << 20)) ? (16L << 20) : 0;
+    const long tail_bytes = (gemm_workspace != nullptr && gemm_workspace_bytes >= (64L << 20)) ? (16L << 20) : 0;
     char* const tail_ws = tail_bytes > 0 ? (char*)gemm_workspace + (gemm_workspace_bytes - tail_bytes) / 256 * 256 : nullptr;
     const long side_ws_bytes = tail_bytes > 0 ? (long)(tail_ws - (char*)gemm_workspace) : gemm_workspace_bytes;
     std::vector<float*> side(L, nullptr);
-    if (!per_layer_join)
-        for (int l = 0; l < L; ++l) side[l] = top.take(side_floats(m, b, l));
+    for (int l = 0; l < L; ++l) side[l] = top.take(side_floats(m, b, l));
     float* const head_buf = top.take(head_floats(m, B));
     float* const head_colsum_ws = top.take(head_colsum_floats(m, B));
     float* const rest = scratch + top.used;
@@ -570,7 +528,7 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         constexpr bool leaves_aside = true;
         // the leaves go to the weight-gradient stream behind the fork the LAST layer's backward makes anyway (a fork of their own
         // was one more event on the chain's stream: ~7 us); without a side stream for them: here, in line
-        leaves_pending = !per_layer_join && leaves_aside && l_hi == L && l_hi > l_lo;
+        leaves_pending = leaves_aside && l_hi == L && l_hi > l_lo;
         if (!leaves_pending) TRY(head_leaves(stream));
         // readout backward -> dL/dh_L
         TRY(i3d_segment_readout_bwd(gy, c->h[L], b.graph_ptr, B, F, m.readout_ops, m.n_readout, gh[L & 1], stream));
@@ -580,10 +538,13 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
     for (int l = l_hi - 1; l >= l_lo; --l) {
         I3dPnaLayerArgs& a = c->layers[l];
         Bump ar(rest);
-        Bump own(side[l]);
-        Bump& sd = per_layer_join ? ar : own;       // where the side stream's buffers of this layer live
-        a.defer_join = per_layer_join ? 0 : 1;
-        a.wgrad_split = (split_wgrad() == 2 || (l == 0 && split_wgrad() == 1)) ? 1 : 0;
+        Bump sd(side[l]);       // the side stream's buffers of this layer
+        a.defer_join = 1;
+        // The first layer's weight gradients (the last ones of a backward pass, and what the step waits for at its very end) as two
+        // launches, the posttrans products early, next to that layer's chain: only the pretrans / bond-table products are left when
+        // the chain ends (2.141 against 2.152 ms, tools/ab.sh, 5 interleaved runs; every layer split that way loses 40 us: one more
+        // launch + reduction per layer for work that was hidden anyway)
+        a.wgrad_split = l == 0 ? 1 : 0;
         // a residual layer accumulates dL/dh_in on top of the incoming gradient IN PLACE (dh_in = dh_out + ...: the separate
         // add pass over [N, F] is gone, composite.hip: i3d_pna_layer_bwd); others ping-pong between the two buffers
         const int cur = c->gh_cur, nxt = a.residual ? cur : cur ^ 1;
@@ -598,7 +559,6 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         g.grad_WD = sd.take((long)b.n_groups * F * g.agg_width);
         g.grad_h = gh[nxt];
         g.grad_agg = ar.take((long)N * g.agg_width);
-        g.tail.bias_partial = defer_bias() ? sd.take(i3d_bn_bias_partial_floats(F)) : nullptr;
         const int f_msg = a.n_pre_extra > 0 ? a.pre[a.n_pre_extra - 1].f_out : a.edge.f_out;
         a.grad_msg = ar.take((long)E * f_msg);
         const float* gy = a.grad_msg;
@@ -610,7 +570,6 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
             fc.grad_y = gy;
             fc.grad_pre = sd.take((long)E * fc.f_out);
             fc.grad_x = ar.take((long)E * fc.f_in);
-            fc.tail.bias_partial = defer_bias() ? sd.take(i3d_bn_bias_partial_floats(fc.f_out)) : nullptr;
             gy = fc.grad_x;
         }
         I3dEdgeFcArgs& e = a.edge;
@@ -620,12 +579,10 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         e.grad_y = gy;
         e.grad_pre = sd.take((long)E * e.f_out);
         e.grad_P = sd.take((long)N * 2 * e.f_out);
-        a.DL = a.merge_h ? sd.take((long)N * (2 * e.f_out + F)) : nullptr;
+        a.DL = sd.take((long)N * (2 * e.f_out + F));
         e.grad_h = ar.take((long)N * F);
         e.grad_Q = sd.take((long)b.v_pad * e.f_out);
-        e.tail.bias_partial = defer_bias() ? sd.take(i3d_bn_bias_partial_floats(e.f_out)) : nullptr;
-        // (the buffer side_floats() counts for the edge block's bias partials: taken by exactly one of the two)
-        a.edge_bias_partial = (a.merge_h && !defer_bias()) ? sd.take(i3d_bn_bias_partial_floats(e.f_out)) : nullptr;
+        a.edge_bias_partial = sd.take(i3d_bn_bias_partial_floats(e.f_out));
         e.grad_q = grad_table;
         e.grad_q_accumulate = (l == L - 1) ? 0 : 1;        // the bond table feeds every layer: its gradient is their sum
         TRY(i3d_pna_layer_bwd(&a, stream));
@@ -638,7 +595,7 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         }
     }
     if (part == 1) {
-        if (!per_layer_join) TRY(i3d_wgrad_stream_join(stream));
+        TRY(i3d_wgrad_stream_join(stream));
         return I3D_OK;
     }
     // ---- encoders: embedding-table gradients as multi-hot^T dY (deterministic, csrc/edge.hip: multihot_kernel).  The atom
@@ -678,10 +635,10 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         // join (behind it, it was one more cross-stream hop - ~10 us - between the last panel reduction and Adam)
         void* bst = stream;
         constexpr bool bond_aside = true;
-        if (bond_aside && !per_layer_join && own_ws && c->hot_ready) TRY(i3d_wgrad_stream_peek(stream, &bst));
+        if (bond_aside && own_ws && c->hot_ready) TRY(i3d_wgrad_stream_peek(stream, &bst));
         if (bst != stream)
             TRY(wgrad(ob, F, b.n_comb, hotb, vb, grad_table, F, m.grad_bond_tables, F, gemm_workspace, side_ws_bytes, bst));
-        if (!per_layer_join) TRY(i3d_wgrad_stream_join(stream));
+        TRY(i3d_wgrad_stream_join(stream));
         if (!own_ws) TRY(atom_tables(gemm_workspace, gemm_workspace_bytes));
         if (bst == stream)
             TRY(wgrad(ob, F, b.n_comb, hotb, vb, grad_table, F, m.grad_bond_tables, F, gemm_workspace, gemm_workspace_bytes, stream));

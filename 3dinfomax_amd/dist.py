@@ -160,10 +160,6 @@ def _all_ok(ok, group):
     return all(flags)
 
 
-# I3D_PEER_SELFTEST=0: skip the pattern exchange at set-up (world > 1 only; ~100 small launches)
-PEER_SELFTEST = True
-
-
 def _peer_selftest(L, state, device, with_side):
     """Pattern exchange through the installed peer provider (default context on the current stream, the 3D network's context on
     its side stream): all-gathers and fp64 rank-order sums of values every rank can predict, payload sizes from one word to the
@@ -299,7 +295,7 @@ def enable_native_sync(group, device, provider=None, timeout_s=0.0):
                 state['keep'].append(side_scratch)
                 ok = L.i3d_peer_bind_stream(side, ctypes.c_void_p(streams.side_stream(device).cuda_stream), side_scratch.data_ptr(),
                                             side_scratch.numel()) == 0
-        if _all_ok(ok, group) and world > 1 and PEER_SELFTEST:
+        if _all_ok(ok, group) and world > 1:
             # Before any BatchNorm depends on it: exchange known patterns through BOTH contexts and compare bit for bit.  The
             # protocol rests on properties of the fabric nobody could test without a multi-GPU node (an 8-byte system-scope
             # store arrives whole at a peer's uncached memory; mapped mailboxes of another device are pollable): if they do
@@ -456,10 +452,6 @@ def setup(modules, loss=None, group=None, sync_bn=False, broadcast=True):
     return group
 
 
-# I3D_OVERLAP_ALLREDUCE=0: one all-reduce of the whole gradient buffer after the backward pass (round-1 behaviour)
-OVERLAP_ALLREDUCE = True
-
-
 class GradReducer:
     """C2: SUM all-reduce of all parameter gradients through ONE persistent flat buffer.
 
@@ -486,7 +478,7 @@ class GradReducer:
         self.early_spans = []                         # [start, end) element ranges reduced early, fixed by the model structure
         self.early_module = None                      # id() of the ONE module whose backward pass may start them
         self._late, self._late_used = None, False     # gradients that arrive for a slice AFTER its early all-reduce started
-        self.overlap = OVERLAP_ALLREDUCE
+        self.overlap = True                           # False: one all-reduce of the whole buffer after the backward pass
         self._agreed = None                           # None: not checked yet; True / False: every rank has the same early plan
         self._tape = tape
 

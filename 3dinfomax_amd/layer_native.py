@@ -19,17 +19,14 @@ from .layers import _keeps_pre, _set_workspaces
 
 # I3D_NATIVE_LAYER=0: the layer as four block composites sequenced from Python (pna.PNALayerFn)
 NATIVE_LAYER = True
-# I3D_FUSED_BN=0: round-1 form of the layer (statistics pass + apply pass per block); default: BatchNorm statistics in the
-# producers' epilogues, BatchNorm-apply in the consumers' loads (csrc/fused_bn.hip).  Same arithmetic up to summation order.
-FUSED_BN = True
-# I3D_MERGE_H=0: the products that read the node features as separate GEMMs (csrc/model.hip reads the same switch)
-MERGE_H = True
 _SIMPLE_ACTS = (None, 'relu', 'leakyrelu')
 KEEP_LAST_ARGS = None
 
 
 def fused_bn_ok(plan, params, n_pre, n_post):
-    if not FUSED_BN or n_post != 1:
+    """Can the layer take the fused-BatchNorm form (statistics in the producers' epilogues, BatchNorm-apply in the consumers'
+    loads: csrc/fused_bn.hip)?  Otherwise: a statistics pass + an apply pass per block.  Same arithmetic up to summation order."""
+    if n_post != 1:
         return False
     for spec in plan.pre_specs + plan.post_specs[:1]:
         if spec.act not in _SIMPLE_ACTS:
@@ -126,7 +123,7 @@ def forward(ctx, h, q, index, qmap, plan, params):
         n_stats = int(L.i3d_pna_layer_stats_floats(N, E, rows_d.shape[0], f_max))
         total += _al(n_stats)
     total += _al(N * A) + _al(nG * Fp0 * A)
-    merged = fused and n_post == 1 and MERGE_H and Fp0 % 4 == 0          # csrc/composite.hip: merge_h_ok
+    merged = fused and n_post == 1 and Fp0 % 4 == 0          # csrc/composite.hip: merge_h_ok
     WL = 2 * Fo0 + Fp0
     if merged:
         total += _al(WL * Fh) + _al(WL) + _al(N * WL)

@@ -32,8 +32,6 @@ PNA_AGGREGATORS = {k: v for k, v in ops.AGG.items()}
 PNA_SCALERS = {k: v for k, v in ops.SCALER.items()}
 
 
-# I3D_GROUPED_POSTTRANS=0 selects the reference-shaped path ([N,12F] aggregate + K=13F posttrans GEMM)
-GROUPED_POSTTRANS = True
 # I3D_FUSED_LAYER=0 runs a PNA layer as four autograd nodes (edge FC, FC, aggregate, posttrans) instead of one
 FUSED_LAYER = True
 # I3D_EDGE_TABLE=0 materialises the [E, F] bond embeddings and multiplies them by W_q in every layer (reference shape)
@@ -348,7 +346,8 @@ class PNALayer(nn.Module):
                 ef_sorted = tape.apply(_AppendSqDistFn, ef_sorted if self.edge_features else None, g.ndata['x'], idx)
             has_q, qmap = True, None
         avg = float(self.avg_d["log"])
-        grouped = GROUPED_POSTTRANS and len(self.scalers) > 1 and h.shape[1] % 4 == 0
+        # degree-grouped posttrans; one scaler or an odd width: the reference-shaped path ([N, 12F] aggregate + K = 13F GEMM)
+        grouped = len(self.scalers) > 1 and h.shape[1] % 4 == 0
         if FUSED_LAYER and h.is_cuda:
             # per call: only the per-degree scaler coefficients depend on the batch (cached on its index: the layers of a
             # model share them); specs and parameters come from the FC layers' hot caches

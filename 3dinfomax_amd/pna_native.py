@@ -41,7 +41,7 @@ def _fc_ok(fc, need_bn):
 
 def eligible(module, g):
     """cheap per-call checks; the structural ones are cached on the module"""
-    if not (NATIVE_MODEL and layer_native.FUSED_BN and layer_native.NATIVE_LAYER):
+    if not (NATIVE_MODEL and layer_native.NATIVE_LAYER):
         return False
     # training mode (with or without autograd: the reference's inference.py runs train-mode BatchNorm under no_grad), or
     # eval mode without autograd - the validation pass of trainer/trainer.py:72-78 (BatchNorm with running statistics,
@@ -52,7 +52,7 @@ def eligible(module, g):
         return False
     from . import layers as _layers
     from . import pna as P
-    if not (P.GROUPED_POSTTRANS and P.FUSED_LAYER and P.EDGE_TABLE and _layers.COMPOSITE):      # A/B switches of the tests
+    if not (P.FUSED_LAYER and P.EDGE_TABLE and _layers.COMPOSITE):      # A/B switches of the tests
         return False
     plist = tape._param_list(module)           # a new list object whenever a sub-module / parameter was replaced
     ent = module.__dict__.get('_i3d_native_ok')

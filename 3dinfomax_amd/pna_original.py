@@ -16,24 +16,13 @@ import torch.nn as nn
 
 from . import _lib, layers as _layers, ops, tape
 from .graph import as_batched_graph
-from .layers import (MLP, AggregateFn, BNSpec, Concat2FCFn, EdgeFCFn, FCFn, FCSpec, GroupedConcat2FCFn, ReadoutFn,
+from .layers import (MLP, AggregateFn, BNSpec, EdgeFCFn, FCFn, FCSpec, GroupedConcat2FCFn, ReadoutFn,
                      dropout as _dropout)
 from .mol_encoder import AtomEncoder, BondEncoder
 from .pna import _AppendSqDistFn, _codes, _GatherRowsFn, _scaler_coef
 
 # I3D_TOWER_STACK=0: the towers of a layer one after the other (one autograd node per block and tower: the first version)
 TOWER_STACK = True
-# I3D_TOWER_PAD=0: the stacked layers at the model's own widths (hidden_dim 90 / edge_hidden_dim 70 of the yml: every kernel of the
-# layer in its unaligned form - 4.8 ms per step at batch 512 against the padded form's)
-PAD_WIDTHS = True
-# I3D_TOWER_BLOCKS=0: the posttrans products of a stacked layer as ONE dense product on the zero-padded stacked weight instead of
-# `towers` diagonal blocks
-TOWER_BLOCKS = True
-# I3D_TOWER_FOLD=0: the aggregation of a stacked layer with all its scaler blocks ([N, 12 F]) instead of the scalers folded into
-# per-degree posttrans weights as in the 2D network (the aggregation writes its identity blocks only, K of the products on it is
-# n_scalers times shorter, the aggregated tensor n_scalers times smaller; with I3D_TOWER_BLOCKS the per-degree weights' diagonal
-# blocks are multiplied, without it one dense grouped product)
-TOWER_FOLD = True
 
 
 class _RowScaleFn(torch.autograd.Function):
@@ -229,7 +218,7 @@ class PNAOriginal(nn.Module):
             # (an eval-mode layer under a tape may still be differentiated: that backward is sequenced by the block path only)
             native = (TOWER_NATIVE and (layer.training or tape.active() is None) and ops.GEMM_WORKSPACE_BYTES > 0
                       and idx.num_edges > 0       # (a batch without bonds: the block path handles E = 0)
-                      and (not st.fold or _fold_fits(idx, tw)))      # (> 32 distinct in-degrees: the block path has no such table)
+                      and _fold_fits(idx, tw))      # (> 32 distinct in-degrees: the block path has no such table)
             if native:
                 if tw.graph_norm and snorm_flat is None:
                     snorm_flat = snorm.reshape(-1).contiguous().float()
@@ -240,14 +229,11 @@ class PNAOriginal(nn.Module):
                         _layers._bump(c)
                 continue
             msg = tape.apply(EdgeFCFn, h, e_sorted if tw.edge_features else None, st.Wp, st.bp, None, None, idx, st.pre_spec, None)
-            if st.fold:       # identity blocks only, the scalers in per-degree weights (the columns of st.Wq are laid out for it)
-                agg = tape.apply(AggregateFn, msg, idx, tw.aggregators, [ops.SCALER['identity']], float(tw.avg_d), False,
-                                 st.Fip if st.tower_major else 0)
-                coef = [[_scaler_coef(sc, deg, float(tw.avg_d)) for sc in tw.scalers] for deg, _, _ in idx.degree_groups()[2]]
-                x = tape.apply(GroupedConcat2FCFn, h, agg, st.Wq, st.bq, st.gamma, st.beta, None, idx, coef, st.post_spec(layer.training))
-            else:
-                agg = tape.apply(AggregateFn, msg, idx, tw.aggregators, tw.scalers, float(tw.avg_d), True, st.Fip if st.tower_major else 0)
-                x = tape.apply(Concat2FCFn, h, agg, st.Wq, st.bq, st.gamma, st.beta, None, st.post_spec(layer.training))
+            # identity blocks only, the scalers in per-degree weights (the columns of st.Wq are laid out for it)
+            agg = tape.apply(AggregateFn, msg, idx, tw.aggregators, [ops.SCALER['identity']], float(tw.avg_d), False,
+                             st.Fip if st.tower_major else 0)
+            coef = [[_scaler_coef(sc, deg, float(tw.avg_d)) for sc in tw.scalers] for deg, _, _ in idx.degree_groups()[2]]
+            x = tape.apply(GroupedConcat2FCFn, h, agg, st.Wq, st.bq, st.gamma, st.beta, None, idx, coef, st.post_spec(layer.training))
             if layer.training:
                 for c in st.counters:
                     _layers._bump(c)
@@ -287,17 +273,16 @@ class _LayerStack:
         B = len(towers[0].aggregators) * len(towers[0].scalers)
         assert fc_post.in_dim == (B + 1) * Fi and fc_pre.out_dim == Fi and fc_post.out_dim == Fo
         self.has_bn = fc_post.batch_norm is not None
-        pad = (lambda n: (n + 3) & ~3) if PAD_WIDTHS else (lambda n: n)          # noqa: E731
         pad4 = lambda n: (n + 3) & ~3                                            # noqa: E731
-        Dp, Fep, Fip, Fop, Mix = pad(D), pad(Fe), pad(Fi), pad(Fo), layer.out_dim
-        Mixp = pad(Mix)
+        Dp, Fep, Fip, Fop, Mix = pad4(D), pad4(Fe), pad4(Fi), pad4(Fo), layer.out_dim
+        Mixp = pad4(Mix)
         self.D, self.Dp, self.Fe, self.Fep, self.Mix, self.Mixp = D, Dp, Fe, Fep, Mix, Mixp
         # the aggregated columns tower-major ([tower][block][feature]): a tower's B blocks are one K range, the posttrans products on
-        # them run as T diagonal blocks (csrc/tower.hip, i3d_gemm_f32_batched) - needs the per-tower widths padded
+        # them run as T diagonal blocks (csrc/tower.hip, i3d_gemm_f32_batched) - needs the per-tower widths padded.  The aggregation
+        # writes its identity blocks only, the scalers are folded into per-degree posttrans weights as in the 2D network (K of the
+        # products on it is n_scalers times shorter; csrc/grouped.hip builds those weights with 16-byte accesses: padded widths)
         self.T, self.Fip = T, Fip
-        # (csrc/grouped.hip builds the per-degree weights with 16-byte accesses)
-        self.fold = TOWER_FOLD and Dp % 4 == 0 and (T * Fip) % 4 == 0
-        self.tower_major = TOWER_BLOCKS and T > 1 and Fip % 4 == 0 and Fop % 4 == 0
+        self.tower_major = T > 1
         Mp, Kp, Mq, Kq = T * Fip, 2 * Dp + Fep, T * Fop, Dp + B * T * Fip
         ldp, ldq, ldm = pad4(Kp), pad4(Kq), Mq        # (csrc/tower.hip takes the mixing weights contiguous)
         sizes = [Mp * ldp, pad4(Mp), Mq * ldq, pad4(Mq), pad4(Mq), pad4(Mq), pad4(Mixp * ldm), pad4(Mixp)]
@@ -344,10 +329,8 @@ class _LayerStack:
             self.param_blocks.append((W2, 0, Fo, Fi, Kp_t(W2), 'Wq', t * Fop, c0))
             for k in range(B):
                 nA = len(towers[0].aggregators)
-                if self.tower_major and self.fold:      # [scaler][tower][aggregator][feature]
+                if self.tower_major:                    # [scaler][tower][aggregator][feature]
                     col = Dp + (k // nA) * (T * nA * Fip) + t * (nA * Fip) + (k % nA) * Fip
-                elif self.tower_major:                  # [tower][block][feature]
-                    col = Dp + t * B * Fip + k * Fip
                 else:                                   # [block][tower][feature]
                     col = Dp + k * T * Fip + t * Fip
                 self.param_blocks.append((W2, Fi + k * Fi, Fo, Fi, Kp_t(W2), 'Wq', t * Fop, col))
@@ -550,16 +533,15 @@ class _TowerLayerFn(torch.autograd.Function):
         a.avg_d_log = float(tw.avg_d)
         a.residual, a.training = int(layer.residual), int(training)
         a.n_towers = st.T if st.tower_major else 0
-        if st.fold:
-            rows, tiles, groups = idx.degree_groups()
-            nS = len(tw.scalers)
-            assert _fold_fits(idx, tw), 'the caller (_forward_stacked) sends such a batch through the block path'
-            a.n_deg_groups, a.m_padded = len(groups), rows.shape[0]
-            for gi, (deg, start, count) in enumerate(groups):
-                a.group_start[gi], a.group_count[gi] = start, count
-                for si, sc in enumerate(tw.scalers):
-                    a.coef[gi * nS + si] = _scaler_coef(sc, deg, float(tw.avg_d))
-                a.deg_rows, a.deg_tile_group = rows.data_ptr(), tiles.data_ptr()
+        rows, tiles, groups = idx.degree_groups()
+        nS = len(tw.scalers)
+        assert _fold_fits(idx, tw), 'the caller (_forward_stacked) sends such a batch through the block path'
+        a.n_deg_groups, a.m_padded = len(groups), rows.shape[0]
+        for gi, (deg, start, count) in enumerate(groups):
+            a.group_start[gi], a.group_count[gi] = start, count
+            for si, sc in enumerate(tw.scalers):
+                a.coef[gi * nS + si] = _scaler_coef(sc, deg, float(tw.avg_d))
+        a.deg_rows, a.deg_tile_group = rows.data_ptr(), tiles.data_ptr()
         a.h, a.e = h.data_ptr(), (e.data_ptr() if e is not None else None)
         a.snorm = snorm.data_ptr() if snorm is not None else None
         a.Wp, a.bp, a.Wq, a.bq = Wp.data_ptr(), bp.data_ptr(), Wq.data_ptr(), bq.data_ptr()

@@ -58,7 +58,7 @@ extern "C" {
 #define I3D_SCALE_AMPLIFICATION 1
 #define I3D_SCALE_ATTENUATION 2
 
-int i3d_abi_version(void);
+int i3d_abi_version(void); /* 2 (1 -> 2: I3dBnTail lost its last member, the deferred-bias entry points are gone) */
 const char* i3d_last_error(void);
 
 /* ---- K1: fused multi-table embedding sum -----------------------------------------------------------
@@ -515,16 +515,15 @@ int i3d_gemm_f32_fused_bf16out(int M, int N, int K, const float* A, int lda, lon
 /* Wcat [2 f_out_edge + f_out_post, f_h] = [W_s ; W_d ; W_h], bcat = [0 | 0 | bias_post] (I3dPnaLayerArgs.merge_h) */
 int i3d_pna_pack_h_weights(const float* W_edge, int ldw_edge, int f_out_edge, const float* W_post, int ldw_post, int f_out_post,
                            const float* bias_post, int f_h, float* Wcat, float* bcat, void* stream);
-/* i3d_bn_bwd_deferred_bias (local statistics or the process-wide collectives) with grad_pre as a column block of a wider
+/* i3d_bn_bwd (local statistics or the process-wide collectives) with grad_pre as a column block of a wider
  * matrix: row pitch ld_out floats */
 int i3d_bn_bwd_strided(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act, int post_act,
                        const float* mean, const float* invstd, const float* gamma, const float* beta, float* grad_gamma,
-                       float* grad_beta, float* grad_pre, int ld_out, float* grad_bias, void* workspace, float* bias_partial,
-                       void* stream);
+                       float* grad_beta, float* grad_pre, int ld_out, float* grad_bias, void* workspace, void* stream);
 /* i3d_bn_bwd with the BatchNorm input x stored as bf16 (row r at (bf16*)x + r * feat) */
 int i3d_bn_bwd_x_bf16(const float* grad_y, const void* x, int rows, int feat, int act, int post_act, const float* mean,
                       const float* invstd, const float* gamma, const float* beta, float* grad_gamma, float* grad_beta, float* grad_pre,
-                      float* grad_bias, void* workspace, float* bias_partial, void* stream);
+                      float* grad_bias, void* workspace, void* stream);
 /* dW[f_out,f_in] = dY^T y for y = (x - mean) * scale + shift (aff over f_in) computed from the raw x; grad_bias[f_out] =
  * column sums of dY (already computed) */
 int i3d_gemm_f32_wgrad_bn(int f_out, int f_in, int rows, const float* dY, int ldy, const float* x, int ldx, float* dW,
@@ -532,7 +531,7 @@ int i3d_gemm_f32_wgrad_bn(int f_out, int f_in, int rows, const float* dY, int ld
                           void* stream);
 /* ---- synchronised BatchNorm from inside the sequencers: process-wide collectives (csrc/comm.hip) ---------------------
  * The reference's BatchNorm statistics are over the whole batch (models/base_layers.py:87, 100-111); with the batch
- * sharded over ranks, i3d_bn_finalize_partials, i3d_act_stats_fwd[_counted] (sums_out NULL) and i3d_bn_bwd[_deferred_bias]
+ * sharded over ranks, i3d_bn_finalize_partials, i3d_act_stats_fwd[_counted] (sums_out NULL) and i3d_bn_bwd
  * (sums_out / sums_in NULL) synchronise their statistics over the ranks WHILE a collective table is set: local merge ->
  * collective on the caller's stream -> finalisation over all ranks (running statistics = global, grad_gamma / grad_beta =
  * this rank's share: the gradient all-reduce sums them).  world 1 runs the same sequence (self-test).
@@ -651,19 +650,13 @@ int i3d_pna_aggregate_bwd_ex(const float* grad_out, const void* e, int e_bf16, c
                              int force_scalers, float avg_d_log, float* grad_e, void* stream);
 
 /* The BatchNorm backward (i3d_bn_bwd and its variants; reference models/base_layers.py:100-111 under autograd) as ONE launch for
- * tensors of up to 256 * (4096 / feat) * 4 rows, feat % 4 == 0, feat <= 512, activations none / ReLU / LeakyReLU: a workgroup
+ * tensors of up to 256 * (2048 / feat) * 8 rows, feat % 4 == 0, feat <= 2048, activations none / ReLU / LeakyReLU: a workgroup
  * keeps its row chunk in registers across an in-launch reduction (every workgroup of the launch is resident: <= 256 workgroups,
  * two per CU).  Process-wide, on by default (environment I3D_BN_BWD_ONE_LAUNCH=0); switch it OFF when several processes share
  * one GPU (their launches compete for the CUs and the residency argument no longer holds).  Returns the previous setting. */
 int i3d_set_bn_bwd_one_launch(int on);
 int i3d_bn_bwd_one_launch_supported(int rows, int feat); /* 1: a local (not synchronised) i3d_bn_bwd of this shape takes it */
-/* i3d_bn_bwd with the finalisation of grad_bias deferred (bias_partial != NULL): see I3dBnTail.bias_partial */
-long i3d_bn_bias_partial_floats(int feat);
-int i3d_bn_bwd_deferred_bias(const float* grad_y, const float* x, const float* pre, int rows, int feat, int act, int post_act,
-                             const float* mean, const float* invstd, const float* gamma, const float* beta,
-                             float* grad_gamma, float* grad_beta, float* grad_pre, float* grad_bias, double* sums_out,
-                             const double* sums_in, long total_rows, void* workspace, float* bias_partial, void* stream);
-int i3d_bn_bias_finalize(const float* bias_partial, int rows, int feat, float* grad_bias, void* stream);
+long i3d_bn_bias_partial_floats(int feat); /* floats of the partials buffer i3d_colsum_strided takes */
 /* The BatchNorm backward of a PNA layer's edge block (the FCLayer inside pretrans_edges, reference models/pna.py:237-252 with
  * models/base_layers.py:100-111) fused with the two segmented sums behind it: column sums of dy and dy xhat as i3d_bn_bwd (one
  * launch; grad_gamma / grad_beta), then ONE launch that forms the data gradient g of every edge row inside the sums that consume
@@ -699,8 +692,6 @@ typedef struct {
     void* gemm_workspace; /* scratch of the weight-gradient GEMMs of the backward (i3d_gemm_f32_ws), may be NULL */
     long gemm_workspace_bytes;
     long long* num_batches_tracked; /* BatchNorm1d's int64 counter, incremented by the forward (may be NULL) */
-    float* bias_partial; /* backward, optional (i3d_bn_bias_partial_floats(f_out) floats): the bias gradient is finalised
-                          * from these partials next to the weight gradients instead of inside the data-gradient pass */
 } I3dBnTail;
 
 typedef struct { /* y = tail(x W^T + b) */

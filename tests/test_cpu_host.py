@@ -24,7 +24,7 @@ def test_build_entry_compiles_and_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f'{name} declared in include/infomax3d_hip.h but not exported'
     assert set(declared) == set(L._SIGNATURES), 'ctypes signature table out of sync with the header'
-    assert lib.i3d_abi_version() == 1
+    assert lib.i3d_abi_version() == 2
     # argument validation happens on the host before any launch: no GPU needed
     rc = lib.i3d_gemm_f32(0, 0, -1, 4, 4, None, 4, None, 4, None, 4, None, 0, None)
     assert rc == -1 and b'negative dimension' in lib.i3d_last_error()

@@ -565,7 +565,7 @@ def test_bn_bwd_one_launch_against_the_two_pass_kernels(rows, feat, act, post):
             p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
             ops.check(L.load().i3d_bn_bwd_strided(p(dyg), p(xg), None, rows, feat, L.ACT[act], L.ACT[post], p(mg), p(ig), p(gg_), p(bg), p(gg3), p(gb3),
                                                   ctypes.c_void_p(wide.data_ptr() + 4 * 8), feat + 12, p(gbias), p(ops._workspace(feat, xg.device)),
-                                                  None, ops._stream()), 'i3d_bn_bwd_strided')
+                                                  ops._stream()), 'i3d_bn_bwd_strided')
             assert torch.equal(wide[:, 8:8 + feat], gp1) and torch.all(wide[:, :8] == 3.0) and torch.all(wide[:, 8 + feat:] == 3.0)
             assert torch.all(gbias == 0) and torch.equal(gg3, gg1) and torch.equal(gb3, gb1)
     finally:
