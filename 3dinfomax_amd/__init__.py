@@ -4,8 +4,8 @@ PNA(+Net3D)+NT-Xent behind the reference's model_type / model3d_type / loss_func
 The package name starts with a digit, so import it with importlib.import_module('3dinfomax_amd') or through
 the alias module `infomax3d_amd` at the repository root.
 """
-from .graph import (BatchedMolGraph, GraphIndex, as_batched_graph, batch, bond_graph, complete_graph,  # noqa: F401
-                    conformer_collate, contrastive_collate, graph_collate, pairwise_distance_collate,
+from .graph import (BatchedMolGraph, GraphIndex, NodeDropCollate, as_batched_graph, batch, bond_graph,  # noqa: F401
+                    complete_graph, conformer_collate, contrastive_collate, graph_collate, pairwise_distance_collate,
                     s_norm_contrastive_collate, s_norm_graph_collate)
 from . import synth  # noqa: F401
 
@@ -56,4 +56,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMultiplePositives', 'FCLayer', 'MLP', 'AtomEncoder', 'BondEncoder', 'contrastive_collate',
            'conformer_collate', 'graph_collate', 's_norm_graph_collate', 's_norm_contrastive_collate', 'BatchedMolGraph', 'batch', 'bond_graph', 'complete_graph', 'Adam', 'PositiveSimilarity',
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
-           'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate']
+           'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate',
+           'NodeDropCollate']

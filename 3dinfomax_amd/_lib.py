@@ -126,6 +126,13 @@ class TowerLayerArgs(ctypes.Structure):
                    ('group_count', c_int * 32), ('coef', c_float * 128), ('deg_rows', _P), ('deg_tile_group', _P)])
 
 
+class NodeDropView(ctypes.Structure):
+    _fields_ = ([('keep', _P), ('graph_ptr', _P), ('edge_ptr', _P), ('deg_base', _P), ('pad_range', _P)]
+                + [(n, c_int) for n in ('n_groups', 'num_nodes', 'num_edges', 'rows')]
+                + [(n, _P) for n in ('src', 'dst', 'atom_feat', 'bond_feat', 'in_ptr', 'perm', 'src_s', 'dst_s', 'out_ptr', 'out_epos',
+                                     'inv_perm', 'deg_rows')])
+
+
 ALL_GATHER_F32 = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p)
 ALL_REDUCE_F64 = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_long, c_void_p)
 
@@ -325,6 +332,8 @@ _SIGNATURES = {
     'i3d_pair_sum_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
     'i3d_pair_norm_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
     'i3d_pair_norm_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_node_drop_build': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    POINTER(NodeDropView), c_int, _P]),
 }
 
 _lib = None

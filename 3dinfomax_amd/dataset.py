@@ -138,9 +138,180 @@ class FlatMolDataset:
         return {'buf': torch.from_numpy(buf), 'layout': tuple(layout), 'n': torch.from_numpy(n), 'groups': groups, 'cuts': cuts,
                 'dims': (B, N, E), 'max_indeg': int(indeg.max()) if E else 0}
 
+    def assemble_nodedrop_host(self, ids, drop_ratio=0.2, rng=None, removed=None):
+        """The host half of a pair of node-dropped views of the batch `ids` (the GraphCL baseline's NodeDropCollate, reference
+        datasets/custom_collate.py:230-263): the bond graph of the batch plus, per view, a keep mask and what the device
+        builder (csrc/nodedrop.hip) must be told - per molecule the kept nodes and edges, the degree groups, the deg_rows slot
+        of every (molecule, in-degree), max_in_degree - in ONE packed buffer: one H2D copy, one launch
+        (`nodedrop_to_device`, also reached through BatchStream.to_device).  No per-molecule Python loop.
+        Removal sets: `removed` = (view 1, view 2), each a sequence of one array of local node ids per molecule; otherwise the
+        numpy Generator `rng` draws, per molecule and view, a uniform subset of exactly int(drop_ratio * n) nodes (float64
+        product, truncated as the reference's int(): 0.29 and 100 atoms remove 28)."""
+        ids = np.asarray(ids, dtype=np.int64)
+        n, e = self.n_atoms[ids], self.n_edges[ids]
+        B, N, E = ids.shape[0], int(n.sum()), int(e.sum())
+        node_off = np.cumsum(n) - n
+        edge_off = np.cumsum(e) - e
+        ngi = _ranges(self.atom_start[ids], n)
+        egi = _ranges(self.edge_start[ids], e)
+        e_node_off = np.repeat(node_off, e)
+        e_edge_off = np.repeat(edge_off, e)
+        src = self.src[egi] + e_node_off
+        dst = self.dst[egi] + e_node_off
+        perm = self.perm[egi] + e_edge_off
+        in_ptr = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(self.indeg[ngi], out=in_ptr[1:])
+        out_ptr = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(self.outdeg[ngi], out=out_ptr[1:])
+        graph_ptr = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(n, out=graph_ptr[1:])
+        keep = np.ones((2, N), dtype=bool)
+        if removed is not None:
+            for v in range(2):
+                r = [np.asarray(x, dtype=np.int64).reshape(-1) + o for x, o in zip(removed[v], node_off)]
+                keep[v, np.concatenate(r) if r else np.zeros(0, dtype=np.int64)] = False
+        else:
+            rng = np.random.default_rng() if rng is None else rng
+            k = np.repeat((float(drop_ratio) * n).astype(np.int64), n)
+            slot = np.arange(N, dtype=np.int64) - np.repeat(node_off, n)
+            mol_key = np.repeat(np.arange(B, dtype=np.int64) << 32, n)
+            for v in range(2):
+                # a uniformly random order of every molecule's nodes (molecule-major sort keys); the first k of it go
+                order = np.argsort(mol_key | rng.integers(0, 1 << 32, N, dtype=np.int64))
+                rank = np.empty(N, dtype=np.int64)
+                rank[order] = slot
+                keep[v] = rank >= k
+        cs_off = np.concatenate([node_off, [N]])
+        ce_off = np.concatenate([edge_off, [E]])
+        views, counts = [], []
+        for v in range(2):
+            kv = keep[v]
+            ke = kv[src] & kv[dst]
+            nk = np.concatenate([[0], np.cumsum(kv)])
+            ek = np.concatenate([[0], np.cumsum(ke)])
+            n2, e2 = np.diff(nk[cs_off]), np.diff(ek[ce_off])
+            indeg2 = np.bincount(dst[ke], minlength=N)[kv]
+            counts.append((n2, e2, indeg2))
+        stride = max(int(c[2].max()) + 1 if c[2].size else 1 for c in counts)
+        if stride > 64:
+            raise ValueError(f'node drop: in-degree {stride - 1} > 63 (the device builder gives every in-degree a lane)')
+        i32 = np.concatenate([in_ptr, perm, src[perm], dst[perm], out_ptr, self.out_epos[egi] + e_edge_off, graph_ptr])
+        v32 = []
+        for n2, e2, indeg2 in counts:
+            N2, E2 = int(n2.sum()), int(e2.sum())
+            cnt = np.bincount(indeg2, minlength=stride)
+            degs = np.nonzero(cnt)[0]
+            padded = (cnt + 63) // 64 * 64
+            start = np.cumsum(padded) - padded                          # (groups of absent degrees are empty)
+            table = np.bincount(np.repeat(np.arange(B, dtype=np.int64), n2) * stride + indeg2,
+                                minlength=B * stride).reshape(B, stride)
+            deg_base = np.cumsum(table, 0) - table + start[None, :]
+            pad_range = np.stack([start + cnt, start + padded], 1)[degs]
+            tiles = np.repeat(np.arange(degs.shape[0], dtype=np.int64), padded[degs] // 64)
+            gp2 = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum(n2, out=gp2[1:])
+            ep2 = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum(e2, out=ep2[1:])
+            parts = (gp2, ep2, deg_base.ravel(), pad_range.ravel(), tiles)
+            o = sum(int(a.size) for a in v32)
+            cuts = []
+            for a in parts:
+                cuts.append((o, o + int(a.size)))
+                o += int(a.size)
+                v32.append(a)
+            groups = tuple((int(d), int(start[d]), int(cnt[d])) for d in degs)
+            views.append({'dims': (N2, E2), 'n': torch.from_numpy(n2), 'groups': groups, 'cuts': tuple(cuts),
+                          'max_indeg': int(indeg2.max()) if E2 else 0, 'rows': int(padded.sum())})
+        segs = (('i64', np.concatenate([src, dst, self.atom_feat[ngi].ravel(), self.bond_feat[egi].ravel()])),
+                ('i32', i32.astype(np.int32)), ('keep', keep.astype(np.uint8).ravel()),
+                ('v32', np.concatenate(v32).astype(np.int32)))
+        layout, o = [], 0
+        for name, a in segs:
+            layout.append((name, o, int(a.size)))
+            o += (a.nbytes + 15) & ~15
+        buf = np.zeros(max(o, 16), dtype=np.uint8)
+        for (name, off, cnt), (_, a) in zip(layout, segs):
+            buf[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
+        return {'buf': torch.from_numpy(buf), 'layout': tuple(layout), 'n': torch.from_numpy(n), 'dims': (B, N, E),
+                'node_drop': tuple(views), 'deg_stride': stride, 'max_atoms': int(n.max()) if B else 0,
+                'max_edges': int(e.max()) if B else 0, 'atom_cols': int(self.atom_feat.shape[1]),
+                'bond_cols': int(self.bond_feat.shape[1])}
+
+
+def node_drop_removed(hb):
+    """The removal sets a node-drop host batch (FlatMolDataset.assemble_nodedrop_host) carries: (view 1, view 2), each a list
+    of one array of local node ids per molecule."""
+    B, N, _ = (int(v) for v in hb['dims'])
+    off = {name: (int(o), int(c)) for name, o, c in hb['layout']}['keep']
+    keep = hb['buf'].numpy()[off[0]:off[0] + off[1]].reshape(2, N)
+    n = hb['n'].numpy().astype(np.int64)
+    local = np.arange(N, dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+    split = np.cumsum(n)[:-1]
+    return tuple([r[r >= 0] for r in np.split(np.where(keep[v] == 0, local, -1), split)] for v in range(2))
+
+
+def nodedrop_to_device(hb, device):
+    """-> ([view 1], [view 2]) on `device`: ONE H2D copy of a node-drop host batch and ONE launch of the device builder
+    (csrc/nodedrop.hip).  No host synchronisation.  Each view is what `graph.batch(...)` of the dropped molecules followed by
+    `.to(device)` would give, its GraphIndex with the degree groups filled in."""
+    from . import _lib
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise ValueError('nodedrop_to_device builds the views with HIP kernels: it needs a GPU device')
+    B, N, E = (int(v) for v in hb['dims'])
+    d = _stager(device).to_device(hb['buf'], device)
+    seg = {}
+    for name, off, cnt in hb['layout']:
+        dt = _SEG_DTYPE[name]
+        seg[name] = d[int(off):int(off) + int(cnt) * dt.itemsize].view(dt)
+    d64, d32, keep, v32 = seg['i64'], seg['i32'], seg['keep'], seg['v32']
+    ac, bc = int(hb['atom_cols']), int(hb['bond_cols'])
+    cut = np.cumsum([0, N + 1, E, E, E, N + 1, E, B + 1])
+    in_ptr, perm, src_s, dst_s, out_ptr, out_epos, graph_ptr = (d32[int(a):int(b)] for a, b in zip(cut[:-1], cut[1:]))
+    vs = hb['node_drop']
+    dims = [tuple(int(x) for x in v['dims']) for v in vs]
+    n64 = [(2 + bc) * E2 + ac * N2 for N2, E2 in dims]
+    n32 = [2 * (N2 + 1) + 5 * E2 + int(v['rows']) for (N2, E2), v in zip(dims, vs)]
+    o64 = torch.empty(sum(n64), dtype=torch.int64, device=device)
+    o32 = torch.empty(sum(n32), dtype=torch.int32, device=device)
+    structs = (_lib.NodeDropView * 2)()
+    graphs = []
+    p64 = p32 = 0
+    for k, ((N2, E2), v) in enumerate(zip(dims, vs)):
+        a64 = o64[p64:p64 + n64[k]]
+        a32 = o32[p32:p32 + n32[k]]
+        p64 += n64[k]
+        p32 += n32[k]
+        src2, dst2 = a64[:E2], a64[E2:2 * E2]
+        feat = a64[2 * E2:2 * E2 + ac * N2].view(N2, ac)
+        efeat = a64[2 * E2 + ac * N2:].view(E2, bc)
+        c32 = np.cumsum([0, N2 + 1, E2, E2, E2, N2 + 1, E2, E2, int(v['rows'])])
+        i_ptr, i_perm, i_src, i_dst, o_ptr, o_epos, i_inv, rows = (a32[int(a):int(b)] for a, b in zip(c32[:-1], c32[1:]))
+        gp2, ep2, deg_base, pad_range, tiles = (v32[int(a):int(b)] for a, b in v['cuts'])
+        s = structs[k]
+        s.keep, s.graph_ptr, s.edge_ptr = keep[k * N:].data_ptr(), gp2.data_ptr(), ep2.data_ptr()
+        s.deg_base, s.pad_range = deg_base.data_ptr(), pad_range.data_ptr()
+        s.n_groups, s.num_nodes, s.num_edges, s.rows = len(v['groups']), N2, E2, int(v['rows'])
+        s.src, s.dst, s.atom_feat, s.bond_feat = src2.data_ptr(), dst2.data_ptr(), feat.data_ptr(), efeat.data_ptr()
+        s.in_ptr, s.perm, s.src_s, s.dst_s = i_ptr.data_ptr(), i_perm.data_ptr(), i_src.data_ptr(), i_dst.data_ptr()
+        s.out_ptr, s.out_epos, s.inv_perm, s.deg_rows = o_ptr.data_ptr(), o_epos.data_ptr(), i_inv.data_ptr(), rows.data_ptr()
+        idx = GraphIndex(N2, E2, B, i_ptr, i_perm, i_src, i_dst, o_ptr, o_epos, gp2, i_inv, int(v['max_indeg']), rows, tiles,
+                         tuple(tuple(int(x) for x in gr) for gr in v['groups']))
+        graphs.append(BatchedMolGraph(src2, dst2, N2, v['n'], ndata={'feat': feat}, edata={'feat': efeat}, index=idx))
+    L = _lib.load()
+    stream = torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
+    _lib.check(L.i3d_node_drop_build(d64[:E].data_ptr(), d64[E:2 * E].data_ptr(), d64[2 * E:2 * E + ac * N].data_ptr(),
+                                     d64[2 * E + ac * N:].data_ptr(), in_ptr.data_ptr(), perm.data_ptr(), src_s.data_ptr(),
+                                     dst_s.data_ptr(), out_ptr.data_ptr(), out_epos.data_ptr(), graph_ptr.data_ptr(), B, ac, bc,
+                                     int(hb['max_atoms']), int(hb['max_edges']), int(hb['deg_stride']), structs, 2, stream),
+               'i3d_node_drop_build')
+    for g in graphs:
+        g.mark_ready()
+    return [graphs[0]], [graphs[1]]
+
 
 _SEG_DTYPE = {'i64': torch.int64, 'i32': torch.int32, 'f32': torch.float32, 'rows': torch.int32, 'tiles': torch.int32,
-              'edge_ptr': torch.int32}
+              'edge_ptr': torch.int32, 'keep': torch.uint8, 'v32': torch.int32}
 
 
 class _Stager:
@@ -226,10 +397,15 @@ class BatchStream(torch.utils.data.Dataset):
     """Shuffled batches of a FlatMolDataset as host batches, for `torch.utils.data.DataLoader(stream, batch_size=None,
     num_workers=k, pin_memory=True)`: the numpy assembly runs in the worker processes - where the reference runs its
     per-molecule graph construction (DataLoader workers, train.py:589-600) - and the training process only issues the
-    H2D copies and the device-side complete-graph build (`to_device`).  Item i is batch i of a fixed, seeded sequence."""
+    H2D copies and the device-side complete-graph build (`to_device`).  Item i is batch i of a fixed, seeded sequence.
+    `node_drop=r`: the GraphCL baseline's batches instead (NodeDropCollate(r), reference datasets/custom_collate.py:230-263):
+    the worker draws both views' removal sets (a numpy generator seeded by (seed, i)) and `to_device` gives
+    ([view 1], [view 2]), built on the device (FlatMolDataset.assemble_nodedrop_host, nodedrop_to_device)."""
 
-    def __init__(self, flat: 'FlatMolDataset', batch_size: int, steps: int, seed: int = 0, drop_last: bool = True):
+    def __init__(self, flat: 'FlatMolDataset', batch_size: int, steps: int, seed: int = 0, drop_last: bool = True,
+                 node_drop=None):
         self.flat, self.batch_size, self.steps, self.seed = flat, batch_size, steps, seed
+        self.node_drop = node_drop
         self.per_epoch = max(len(flat) // batch_size, 1) if drop_last else -(-len(flat) // batch_size)
 
     def __len__(self):
@@ -238,11 +414,17 @@ class BatchStream(torch.utils.data.Dataset):
     def __getitem__(self, i):
         epoch, k = divmod(i, self.per_epoch)
         order = np.random.default_rng(self.seed + epoch).permutation(len(self.flat))
-        return self.flat.assemble_host(order[k * self.batch_size:(k + 1) * self.batch_size])
+        ids = order[k * self.batch_size:(k + 1) * self.batch_size]
+        if self.node_drop is not None:
+            return self.flat.assemble_nodedrop_host(ids, self.node_drop, rng=np.random.default_rng([self.seed, i]))
+        return self.flat.assemble_host(ids)
 
     @staticmethod
     def to_device(hb, device):
-        """-> ([g2d], [g3d]) on `device` (the tensors of `hb` are pinned when the loader was built with pin_memory=True)"""
+        """-> ([g2d], [g3d]) on `device` (the tensors of `hb` are pinned when the loader was built with pin_memory=True);
+        ([view 1], [view 2]) for a node-drop batch"""
+        if 'node_drop' in hb:
+            return nodedrop_to_device(hb, device)
         g2, xyz, graph_ptr_dev, n, bnn = host_batch_to_device(hb, device)
         return [g2], [complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)]
 

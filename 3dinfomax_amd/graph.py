@@ -177,6 +177,24 @@ class BatchedMolGraph:
         g.ready_event = self.ready_event
         return g
 
+    def remove_nodes(self, nids) -> 'BatchedMolGraph':
+        """DGL's `remove_nodes` semantics, returned as a NEW graph (DGL changes the graph in place; this one leaves `self` and
+        its frames untouched): the kept nodes are renumbered in ascending order, every edge that touches a removed node is
+        dropped, the kept edges keep their relative order, ndata / edata are sliced to match, and on a batched graph
+        batch_num_nodes loses every molecule's removed nodes.  The kernel index is rebuilt on first use."""
+        nids = torch.as_tensor(nids, dtype=torch.long).reshape(-1).to(self._src.device)
+        keep = torch.ones(self._n, dtype=torch.bool, device=self._src.device)
+        keep[nids] = False
+        new_id = torch.cumsum(keep.long(), 0) - 1
+        ek = keep[self._src] & keep[self._dst]
+        bnn = self._bnn
+        if nids.numel():
+            mol = torch.repeat_interleave(torch.arange(bnn.shape[0], device=bnn.device), bnn)
+            gone = ~keep.to(bnn.device)
+            bnn = bnn - torch.bincount(mol[gone], minlength=bnn.shape[0])
+        return BatchedMolGraph(new_id[self._src[ek]], new_id[self._dst[ek]], int(keep.sum()), bnn,
+                               {k: v[keep] for k, v in self.ndata.items()}, {k: v[ek] for k, v in self.edata.items()})
+
     # ---- kernel index -----------------------------------------------------------------
     def index(self) -> GraphIndex:
         if self._index is None:
@@ -261,6 +279,32 @@ def pairwise_distance_collate(batch_items):
     pidx = torch.cat([torch.as_tensor(p) + off for p, off in zip(pairwise_indices, offsets.tolist())], dim=-1)
     mask = torch.arange(int(n_atoms.max()), device=distances[0].device)[None, :] >= n_atoms[:, None]
     return [g, pidx, mask], torch.cat(distances)
+
+
+class NodeDropCollate:
+    """Mirror of reference datasets/custom_collate.py:230-263 (the GraphCL baseline's collate): items are tuples whose first
+    field is the graph (BatchedMolGraph or DGL-like); for every graph of view 1 in item order, then for every graph of view 2,
+    `torch.randperm(n)` is drawn and its first int(drop_ratio * n) nodes are removed -> ([batched view 1], [batched view 2]).
+    Under the same torch seed the views are exactly the reference's.  Unlike the reference, which removes view 1's nodes
+    from the caller's graphs in place, the items are left unmodified.  The fast path that builds the views on the device
+    from one upload is dataset.BatchStream(..., node_drop=r)."""
+
+    def __init__(self, drop_ratio):
+        self.drop_ratio = drop_ratio
+
+    def __call__(self, batch_items):
+        graphs = [as_batched_graph(item[0]) for item in batch_items]
+        device = graphs[0].device
+        removed = []
+        for _view in range(2):
+            for g in graphs:
+                n_atoms = g.number_of_nodes()
+                perm = torch.randperm(n_atoms, device=device)
+                removed.append(perm[:int(self.drop_ratio * n_atoms)])
+        B = len(graphs)
+        view1 = [g.remove_nodes(r) for g, r in zip(graphs, removed[:B])]
+        view2 = [g.remove_nodes(r) for g, r in zip(graphs, removed[B:])]
+        return [batch(view1)], [batch(view2)]
 
 
 def _snorm_n(graphs):

@@ -1103,6 +1103,36 @@ int i3d_pair_norm_fwd(const float* p, const int* src_s, const int* dst_s, const 
 int i3d_pair_norm_bwd(const float* grad_out, const float* p, const float* dist, const int* src_s, const int* dst_s,
                       const int* perm, int pairs, int feat, float* grad_pair, void* stream);
 
+/* ---- node-dropped views (GraphCL baseline; csrc/nodedrop.hip) -------------------------------------------------------
+ * replaces NodeDropCollate (reference datasets/custom_collate.py:230-263: per graph and view, remove_nodes(randperm(n)[:k]),
+ * then dgl.batch) for a batch already on the device.  DGL's remove_nodes semantics: kept nodes renumbered in ascending order,
+ * every edge touching a removed node dropped, kept edges in their relative order, node / edge features sliced to match.
+ * Input: a block-diagonal batch in the layout of FlatMolDataset.assemble_host: src / dst int64 [E] (edge-id order),
+ * atom_feat int64 [N, atom_cols], bond_feat int64 [E, bond_cols], and its kernel index (in_ptr, perm, src_s, dst_s, out_ptr,
+ * out_epos, graph_ptr [num_graphs + 1]).  Per view, the host supplies the keep mask and what it counted from it: the view's
+ * node / edge offsets per molecule, the first deg_rows slot of every (molecule g, in-degree D) at deg_base[g * deg_stride + D]
+ * (D < deg_stride <= 64), and the -1 padding ranges of the degree groups.  Every output array of a view is written: src, dst,
+ * atom_feat [N', atom_cols], bond_feat [E', bond_cols], the index (in_ptr / out_ptr [N' + 1], perm, src_s, dst_s, out_epos,
+ * inv_perm [E']) and deg_rows [rows], identical to graph.build_index / group_nodes_by_degree(include_zero=True) of the dropped
+ * batch; the view's graph_ptr is its input.  One wave per (molecule, view), one launch, no atomics.  max_atoms / max_edges:
+ * bounds of the molecules' sizes (LDS: 4 (max_atoms + 3 max_edges + 2) bytes <= 64 KiB).  A molecule whose kept counts
+ * differ from the view's offsets is not written. */
+typedef struct {
+    const unsigned char* keep;  /* [N] 1: node kept, 0: removed */
+    const int* graph_ptr;       /* [num_graphs + 1] node offsets of the view */
+    const int* edge_ptr;        /* [num_graphs + 1] edge offsets of the view */
+    const int* deg_base;        /* [num_graphs, deg_stride] */
+    const int* pad_range;       /* [n_groups, 2] [begin, end) of the -1 padding of each degree group */
+    int n_groups, num_nodes, num_edges, rows;
+    int64_t *src, *dst, *atom_feat, *bond_feat;
+    int *in_ptr, *perm, *src_s, *dst_s, *out_ptr, *out_epos, *inv_perm, *deg_rows;
+} I3dNodeDropView;
+int i3d_node_drop_build(const int64_t* src, const int64_t* dst, const int64_t* atom_feat, const int64_t* bond_feat,
+                        const int* in_ptr, const int* perm, const int* src_s, const int* dst_s, const int* out_ptr,
+                        const int* out_epos, const int* graph_ptr, int num_graphs, int atom_cols, int bond_cols,
+                        int max_atoms, int max_edges, int deg_stride, const I3dNodeDropView* views, int n_views,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
