@@ -5,7 +5,8 @@ The package name starts with a digit, so import it with importlib.import_module(
 the alias module `infomax3d_amd` at the repository root.
 """
 from .graph import (BatchedMolGraph, GraphIndex, NodeDropCollate, as_batched_graph, batch, bond_graph,  # noqa: F401
-                    complete_graph, conformer_collate, contrastive_collate, graph_collate, pairwise_distance_collate,
+                    complete_graph, conformer_collate, contrastive_collate, contrastive_vae_collate, graph_collate,
+                    pairwise_distance_collate,
                     s_norm_contrastive_collate, s_norm_graph_collate)
 from . import synth  # noqa: F401
 
@@ -23,7 +24,10 @@ def __getattr__(name):
     if name in ('Net3D', 'Net3DLayer'):
         from . import net3d
         return getattr(net3d, name)
-    if name in ('NTXent', 'NTXentMultiplePositives'):
+    if name == 'Net3DAE':
+        from . import net3d_ae
+        return net3d_ae.Net3DAE
+    if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -45,7 +49,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -57,4 +61,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'conformer_collate', 'graph_collate', 's_norm_graph_collate', 's_norm_contrastive_collate', 'BatchedMolGraph', 'batch', 'bond_graph', 'complete_graph', 'Adam', 'PositiveSimilarity',
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
            'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate',
-           'NodeDropCollate']
+           'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate']

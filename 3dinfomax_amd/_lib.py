@@ -332,6 +332,13 @@ _SIGNATURES = {
     'i3d_pair_sum_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
     'i3d_pair_norm_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
     'i3d_pair_norm_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_pair_mlp_supported': (c_int, [c_int]),
+    'i3d_pair_mlp_workspace_floats': (c_long, [c_int, c_int]),
+    'i3d_pair_mlp_fwd': (c_int, [_P] * 9 + [c_int, c_int, c_int, c_float, c_float] + [_P] * 8),
+    'i3d_pair_mlp_bwd': (c_int, [_P] * 13 + [c_int, c_int, c_int, c_int] + [_P] * 10),
+    'i3d_mse_partial_floats': (c_long, [c_long]),
+    'i3d_mse_fwd': (c_int, [_P, _P, c_long, c_double, _P, _P, _P]),
+    'i3d_mse_bwd': (c_int, [_P, _P, c_long, c_double, _P, _P, _P, _P]),
     'i3d_node_drop_build': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                     POINTER(NodeDropView), c_int, _P]),
 }

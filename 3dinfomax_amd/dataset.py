@@ -83,6 +83,18 @@ class FlatMolDataset:
         mask = (torch.arange(int(n_t.max()))[None, :] >= n_t[:, None]).to(xyz.device)
         return [g2, pairwise_indices, mask], g3.edata['d']
 
+    def assemble_ae(self, ids, device, pin=False):
+        """-> ([g2d], [g3d, pairwise_indices [2, P]], distances [P, 1]) on `device`: the layout `contrastive_vae_collate` returns
+        (reference datasets/custom_collate.py:52-63) for the 3D autoencoder, the pairs being the complete graph's edges in its
+        order.  The pair graph's kernel index rides on pairwise_indices; `distances` is a tensor of its own (Net3DAE overwrites
+        g3d.edata['d'])."""
+        g2, xyz, graph_ptr_dev, n, bnn = self.assemble_2d(ids, device, pin)
+        g3 = complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)
+        src, dst = g3.edges()
+        pairwise_indices = torch.stack([src, dst])
+        pairwise_indices._i3d_pair_index = g3.index()       # pair_head.pair_index
+        return [g2], [g3, pairwise_indices], g3.edata['d'].clone()
+
     def assemble_2d(self, ids, device, pin=False):
         """The bond-graph half (pure numpy + three H2D copies; also usable on the CPU for tests)."""
         return host_batch_to_device(self.assemble_host(ids), device, pin)

@@ -20,25 +20,13 @@ import torch
 from torch import nn
 
 from . import ops, tape
-from .graph import as_batched_graph, build_index
+from .graph import as_batched_graph
 from .layers import MLP, FCFn, FCSpec, bn_counter_scope
+from .pair_head import _PairConcatFn, _PairNormFn, _PairSumHeadFn, _SoftplusSumToPairsFn, pair_index  # noqa: F401
 from .pna import PNAGNN
 
 _LINEAR = FCSpec(None, None)
 _RELU = FCSpec('relu', None)
-
-
-def pair_index(pairwise_indices, graph):
-    """The kernel index (graph.GraphIndex) of the pair graph whose edges are `pairwise_indices` [2, P] over the nodes of `graph`.
-    A batch assembled on the device (dataset.FlatMolDataset.assemble_distance) carries it; otherwise it is built once on the
-    host and kept on the tensor."""
-    idx = getattr(pairwise_indices, '_i3d_pair_index', None)
-    if idx is None:
-        g = as_batched_graph(graph)
-        pi = pairwise_indices.detach().cpu().numpy()
-        idx = build_index(pi[0], pi[1], g.number_of_nodes(), g.batch_num_nodes().cpu().numpy()).to(pairwise_indices.device)
-        pairwise_indices._i3d_pair_index = idx
-    return idx
 
 
 class _MHAFn(torch.autograd.Function):
@@ -75,104 +63,6 @@ class _LayerNormResFn(torch.autograd.Function):
         x, r, gamma, mean, rstd = ctx.saved_tensors
         gz, gg, gb = ops.ln_res_bwd(grad_y.contiguous(), x, r, gamma, mean, rstd)
         return gz, gz, gg, gb, None
-
-
-class _PairSumHeadFn(torch.autograd.Function):
-    """softplus(f([h_i|h_j]) + f([h_j|h_i])) for f = Linear(2H -> T), W = [W_a | W_b]: u = h W_a^T + h W_b^T, then the pair kernel"""
-
-    @staticmethod
-    def forward(ctx, h, W, b, pidx):
-        h = h.contiguous()
-        H = h.shape[1]
-        u = ops.gemm(h, W[:, :H], trans_b=True)
-        ops.gemm(h, W[:, H:], trans_b=True, out=u, accumulate=True)
-        ctx.pidx = pidx
-        ctx.save_for_backward(h, W, b, u)
-        return ops.pair_sum_fwd(u, b, pidx)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        h, W, b, u = ctx.saved_tensors
-        H = h.shape[1]
-        du = ops.pair_sum_bwd(grad_out.contiguous(), u, b, ctx.pidx)
-        gW = torch.empty_like(W)
-        ops.gemm(du, h, trans_a=True, out=gW[:, :H])
-        ops.gemm(du, h, trans_a=True, out=gW[:, H:])
-        gb = ops.colsum(du)           # sum over nodes of du = 2 x sum over pairs: d(2b)/db
-        gh = ops.gemm(du, W[:, :H])
-        ops.gemm(du, W[:, H:], out=gh, accumulate=True)
-        return gh, gW, gb, None
-
-
-class _PairNormFn(torch.autograd.Function):
-    """||p_i - p_j||_2 per pair, [P, 1]"""
-
-    @staticmethod
-    def forward(ctx, p, pidx):
-        p = p.contiguous()
-        d = ops.pair_norm_fwd(p, pidx)
-        ctx.pidx = pidx
-        ctx.save_for_backward(p, d)
-        return d
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        p, d = ctx.saved_tensors
-        return ops.pair_norm_bwd(grad_out.contiguous(), p, d, ctx.pidx), None
-
-
-class _PairConcatFn(torch.autograd.Function):
-    """[h_a | h_b] per pair in the pair graph's epos order: (a, b) = (src, dst), or (dst, src) with `swap` (segment sums of one row)"""
-
-    @staticmethod
-    def forward(ctx, h, pidx, swap):
-        h = h.contiguous()
-        P, H = pidx.num_edges, h.shape[1]
-        one = _ranges(P, h.device)
-        out = torch.empty(P, 2 * H, dtype=torch.float32, device=h.device)
-        first, second = (pidx.dst_s, pidx.src_s) if swap else (pidx.src_s, pidx.dst_s)
-        ops.segment_sum(h, one, first, P, out=out[:, :H])
-        ops.segment_sum(h, one, second, P, out=out[:, H:])
-        ctx.cfg = (pidx, swap, H)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        pidx, swap, H = ctx.cfg
-        g = g.contiguous()
-        gs, gd = (g[:, H:], g[:, :H]) if swap else (g[:, :H], g[:, H:])
-        return ops._pair_node_sums(gs, gd, pidx), None, None
-
-
-class _SoftplusSumToPairsFn(torch.autograd.Function):
-    """softplus(a + b), rows permuted from the pair graph's epos order to pair-id order"""
-
-    @staticmethod
-    def forward(ctx, a, b, pidx):
-        x = ops.add(a.contiguous(), b.contiguous())
-        ctx.pidx = pidx
-        ctx.save_for_backward(x)
-        return ops.gather_rows(ops.act_fwd(x, 'softplus'), pidx.inv_perm)
-
-    @staticmethod
-    def backward(ctx, g):
-        (x,) = ctx.saved_tensors
-        ge = ops.act_bwd(ops.gather_rows(g.contiguous(), ctx.pidx.perm), x, 'softplus')
-        return ge, ge, None
-
-
-_ranges_cache = {}
-
-
-def _ranges(n, device):
-    """int32 [0, 1, ..., n]: the row pointer of n one-row segments"""
-    key = (n, str(device))
-    t = _ranges_cache.get(key)
-    if t is None:
-        if len(_ranges_cache) > 64:
-            _ranges_cache.clear()
-        t = _ranges_cache[key] = torch.arange(n + 1, dtype=torch.int32, device=device)
-    return t
 
 
 class DistancePredictor(nn.Module):

@@ -281,6 +281,19 @@ def pairwise_distance_collate(batch_items):
     return [g, pidx, mask], torch.cat(distances)
 
 
+def contrastive_vae_collate(batch_items):
+    """Mirror of reference datasets/custom_collate.py:52-63 (the 3D autoencoder's collate): items (graph, graph3d,
+    pairwise_indices [2, p], distances [p, 1]) -> ([batched graph], [batched 3D graph, pairwise_indices [2, P] with every
+    molecule's node offset added], distances [P, 1]).  Unlike the reference, which adds the offsets in place, the items' index
+    tensors are not modified."""
+    graphs, graphs3d, pairwise_indices, distances = map(list, zip(*batch_items))
+    g = batch(graphs)
+    n_atoms = g.batch_num_nodes()
+    offsets = torch.cumsum(n_atoms, 0) - n_atoms
+    pidx = torch.cat([torch.as_tensor(p) + off for p, off in zip(pairwise_indices, offsets.tolist())], dim=-1)
+    return [g], [batch(graphs3d), pidx], torch.cat(distances)
+
+
 class NodeDropCollate:
     """Mirror of reference datasets/custom_collate.py:230-263 (the GraphCL baseline's collate): items are tuples whose first
     field is the graph (BatchedMolGraph or DGL-like); for every graph of view 1 in item order, then for every graph of view 2,

@@ -281,3 +281,45 @@ class NTXentMultiplePositives(_NTXentBase):
         if self.uniformity_reg > 0:
             loss = loss + self.uniformity_reg * uniformity_loss(z1, z2v)
         return loss
+
+
+class _MSEFn(torch.autograd.Function):
+    """weight * mean((a - b)^2) as a 0-dim tensor (csrc/pairmlp.hip: block partials summed in a fixed order; the upstream scalar
+    gradient is multiplied in on the device)"""
+
+    @staticmethod
+    def forward(ctx, a, b, weight):
+        a, b = a.contiguous().float(), b.contiguous().float()
+        if a.shape != b.shape:
+            raise ValueError(f'mean squared error of tensors shaped {tuple(a.shape)} and {tuple(b.shape)}')
+        n = a.numel()
+        ctx.scale = float(weight) / n if n else float('nan')
+        ctx.save_for_backward(a, b)
+        return ops.mse_fwd(a, b, ctx.scale).reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, b = ctx.saved_tensors
+        ga, gb = ops.mse_bwd(a, b, ctx.scale, grad_out.contiguous().float(), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return ga, gb, None
+
+
+class NTXentAE(_NTXentBase):
+    """reference commons/losses.py:165-204: forward(z1, z2, distances, distance_pred) -> (contrastive term with the regularisers,
+    reconstruction_reg * mean squared error of the predicted pair distances).  Single process only: the global mean over pairs
+    would need the global pair count."""
+    _eps = 1e-8        # reference :191
+
+    def __init__(self, norm: bool = True, tau: float = 0.5, uniformity_reg=0, variance_reg=0, covariance_reg=0,
+                 reconstruction_reg=1) -> None:
+        super().__init__(norm, tau, uniformity_reg, variance_reg, covariance_reg)
+        self.reconstruction_reg = reconstruction_reg
+
+    def forward(self, z1, z2, distances, distance_pred, **kwargs):
+        if self.group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(self.group) > 1:
+                raise NotImplementedError('NTXentAE on a process group of more than one rank: the reconstruction term is a mean over '
+                                          'the pairs of the global batch, which needs the global pair count')
+        loss = self._regularisers(self._contrastive(z1, z2, 1), z1, z2)
+        return loss, _MSEFn.apply(distances, distance_pred, self.reconstruction_reg)

@@ -884,3 +884,80 @@ def _pair_node_sums(g_src, g_dst, pidx):
     N = pidx.num_nodes
     out = segment_sum(g_src, pidx.out_ptr, pidx.out_epos, N)
     return add_inplace(out, segment_sum(g_dst, pidx.in_ptr, None, N))
+
+
+# ---- 3D autoencoder: fused two-layer pair head, mean squared error (csrc/pairmlp.hip) -----------------------------------------
+PAIR_MLP_MAX_WIDTH = 128
+
+
+def pair_mlp_supported(width):
+    """hidden widths of the two-layer distance_net the fused pair head is built for"""
+    return 1 <= width <= PAIR_MLP_MAX_WIDTH
+
+
+def _pair_mlp_workspace(P, D, device):
+    return torch.empty(_lib.load().i3d_pair_mlp_workspace_floats(P, D), dtype=torch.float32, device=device)
+
+
+def pair_mlp_fwd(AB, b1, gamma, beta, w2, b2, pidx, training, eps, momentum, running_mean=None, running_var=None,
+                 num_batches_tracked=None):
+    """softplus(f([h_s | h_d]) + f([h_d | h_s])) for f = Linear -> ReLU -> BatchNorm -> Linear(D -> 1) from AB = h [W1a | W1b]^T
+    [N, 2D] over the pairs of `pidx` -> (out [P, 1] in pair-id order, stats [4, D] = mean1 | rstd1 | mean2 | rstd2 and coef [2D + 1], both fp64).  Training mode
+    updates the running statistics twice (s->d first) and adds 2 to num_batches_tracked, on the device."""
+    for t in (AB, b1, gamma, beta, w2, b2):
+        _chk(t)
+    P, D = pidx.num_edges, AB.shape[1] // 2
+    dev = AB.device
+    out = torch.empty(P, 1, dtype=torch.float32, device=dev)
+    stats = torch.empty(4, D, dtype=torch.float64, device=dev)
+    coef = torch.empty(2 * D + 1, dtype=torch.float64, device=dev)
+    if P == 0:
+        return out, stats, coef
+    ws = _pair_mlp_workspace(P, D, dev) if training else None
+    nbt = num_batches_tracked if (num_batches_tracked is not None and num_batches_tracked.is_cuda) else None
+    check(_lib.load().i3d_pair_mlp_fwd(_p(AB), _p(b1), _p(gamma), _p(beta), _p(w2), _p(b2), _p(pidx.src_s), _p(pidx.dst_s),
+                                       _p(pidx.perm), P, D, int(bool(training)), float(eps), float(momentum), _p(running_mean),
+                                       _p(running_var), _p(nbt), _p(stats), _p(coef), _p(ws), _p(out), _stream()),
+          'i3d_pair_mlp_fwd')
+    return out, stats, coef
+
+
+def pair_mlp_bwd(grad_out, AB, b1, gamma, beta, w2, stats, coef, pidx, training):
+    """-> (grad_AB [N, 2D], grad_gamma [D], grad_beta [D], grad_w2 [D], grad_b2 [1])"""
+    _chk(grad_out)
+    P, D, N = pidx.num_edges, AB.shape[1] // 2, AB.shape[0]
+    dev = AB.device
+    gAB = torch.empty(N, 2 * D, dtype=torch.float32, device=dev)
+    small = torch.empty(3 * D + 1, dtype=torch.float32, device=dev)
+    gg, gb, gw2, gb2 = small[:D], small[D:2 * D], small[2 * D:3 * D], small[3 * D:]
+    grad_pair = torch.empty(P, dtype=torch.float32, device=dev)
+    bcoef = torch.empty(6 * D + 1, dtype=torch.float64, device=dev)
+    check(_lib.load().i3d_pair_mlp_bwd(_p(grad_out), _p(coef), _p(AB), _p(b1), _p(gamma), _p(beta), _p(w2), _p(pidx.src_s),
+                                       _p(pidx.dst_s), _p(pidx.perm), _p(pidx.in_ptr), _p(pidx.out_ptr), _p(pidx.out_epos), N, P,
+                                       D, int(bool(training)), _p(stats), _p(_pair_mlp_workspace(P, D, dev)), _p(grad_pair),
+                                       _p(bcoef), _p(gAB), _p(gg), _p(gb), _p(gw2), _p(gb2), _stream()),
+          'i3d_pair_mlp_bwd')
+    return gAB, gg, gb, gw2, gb2
+
+
+def mse_fwd(a, b, scale):
+    """scale * sum((a - b)^2) -> [1]; deterministic (block partials summed in order), no host read-back"""
+    _chk(a)
+    _chk(b)
+    n = a.numel()
+    assert b.numel() == n
+    L = _lib.load()
+    partial = torch.empty(L.i3d_mse_partial_floats(n), dtype=torch.float32, device=a.device)
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    check(L.i3d_mse_fwd(_p(a), _p(b), n, float(scale), _p(partial), _p(loss), _stream()), 'i3d_mse_fwd')
+    return loss
+
+
+def mse_bwd(a, b, scale, grad_scale_dev, need_a=True, need_b=True):
+    """-> (grad_a, grad_b) = (2 scale g (a - b), its negation), g = grad_scale_dev[0] multiplied in on the device"""
+    n = a.numel()
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(b) if need_b else None
+    if need_a or need_b:
+        check(_lib.load().i3d_mse_bwd(_p(a), _p(b), n, float(scale), _p(grad_scale_dev), _p(ga), _p(gb), _stream()), 'i3d_mse_bwd')
+    return ga, gb

@@ -80,7 +80,10 @@ class Tape:
                 node[5] = None
 
     def backward(self, out_id, grad):
-        grads = {out_id: (grad, False)}
+        if isinstance(out_id, tuple):             # a model with several outputs: one seed per output that received a gradient
+            grads = {oid: (g, False) for oid, g in zip(out_id, grad) if g is not None}
+        else:
+            grads = {out_id: (grad, False)}
         for fn, ctx, args, needs, oid, _ in reversed(self.nodes):
             ent = grads.pop(oid, None)
             if ent is None:                       # output never used downstream
@@ -127,14 +130,33 @@ class ModelFn(torch.autograd.Function):
             out = run()
         finally:
             _tls.tape = prev
+        if isinstance(out, tuple):                # several outputs (Net3DAE: latent vector and distances)
+            for o in out:
+                tape.release(o)
+            ctx.set_materialize_grads(False)
+            ctx.tape, ctx.out_id, ctx.params = tape, tuple(id(o) for o in out), params
+            ctx.on_side_stream = out[0].is_cuda and streams.on_side_stream(out[0].device)
+            return out
         tape.release(out)
         ctx.tape, ctx.out_id, ctx.params = tape, id(out), params
         ctx.on_side_stream = out.is_cuda and streams.on_side_stream(out.device)
         return out
 
     @staticmethod
-    def backward(ctx, grad):
+    def backward(ctx, *grads):
         streams.invalidate_step()
+        if isinstance(ctx.out_id, tuple):
+            # several outputs: the helper-thread backward below (ASYNC_SIDE_BACKWARD) is not offered, the pass runs on this thread
+            grad = tuple(g.contiguous() if g is not None else None for g in grads)
+            direct = DIRECT_PARAM_GRADS and _plain_leaves(ctx.params)
+            out = _model_backward(ctx, grad, direct)
+            if direct:
+                for p, g in zip(ctx.params, out):
+                    if g is not None:
+                        p.grad = g
+                return (None,) * (2 + len(ctx.params))
+            return (None, None) + tuple(out)
+        grad = grads[0]
         direct = DIRECT_PARAM_GRADS and _plain_leaves(ctx.params)
         if direct and ASYNC_SIDE_BACKWARD and ctx.on_side_stream:
             # The model ran next to another one on the side stream (streams.py: Net3D beside PNA) and autograd has made

@@ -1133,6 +1133,47 @@ int i3d_node_drop_build(const int64_t* src, const int64_t* dst, const int64_t* a
                         int max_atoms, int max_edges, int deg_stride, const I3dNodeDropView* views, int n_views,
                         void* stream);
 
+/* ---- 3D autoencoder (reference models/net3d_VAE.py, commons/losses.py:165-204; csrc/pairmlp.hip) -------------------
+ * The pair head distance_net = FCLayer(2H -> D, ReLU, BatchNorm) -> FCLayer(D -> 1) of reference net3d_VAE.py:116-119
+ * (projection_layers=2): softplus(f([h_s | h_d]) + f([h_d | h_s])) per ordered pair, each of the two calls with its own batch
+ * statistics.  AB [N, 2 D] = h [W1a | W1b]^T is the node-level half of the first Linear (W1 = [W1a | W1b], one GEMM); the pairs
+ * are the edges of a pair graph in its destination-sorted order e, (s, d) = (src_s[e], dst_s[e]), pair id perm[e] (any pair
+ * list, symmetric or not).  x1 = relu(A[s] + B[d] + b1), x2 = relu(A[d] + B[s] + b1) are recomputed wherever they are needed:
+ * no [P, 2H] or [P, D] tensor exists in either direction.  D = width <= 128 (i3d_pair_mlp_supported).
+ * i3d_pair_mlp_fwd: out[perm[e]] = softplus(sum_c w2 BN_1(x1)[c] + w2 BN_2(x2)[c] + 2 b2), out [pairs].  training != 0: batch
+ *   statistics (biased variance) from a blocked fp64 reduction through `workspace` (i3d_pair_mlp_workspace_floats(pairs,
+ *   width) floats), running_mean / running_var updated with the s->d statistics first and the d->s statistics second (unbiased
+ *   variance, `momentum`), num_batches_tracked (int64 on the device, may be null) + 2; pairs >= 2.  training == 0: the running
+ *   estimates for both orders, no reduction, workspace unused.  stats [4, D] (mean1 | rstd1 | mean2 | rstd2) and coef [2 D + 1], fp64
+ *   (constants shared by every pair of a column: their rounding would shift all pairs alike),
+ *   are outputs, and inputs of the backward pass.  pairs == 0: nothing is launched.
+ * i3d_pair_mlp_bwd: from grad_out [pairs] and the forward's stats and coef (o_e, the argument of the softplus, is recomputed
+ *   as the forward computed it): grad_gamma, grad_beta, grad_w2
+ *   [D], grad_b2 [1] and grad_AB [num_nodes, 2 D] (every row written; dh, dW1 and db1 follow on the GEMMs: dh = dA W1a + dB W1b,
+ *   dW1 = [dA^T h | dB^T h], db1 = colsum(dA)).  grad_pair [pairs] (do_e, e order) and bcoef [6 D + 1] (fp64) are scratch; workspace as
+ *   in the forward.  Per node, the in-pairs are summed first (in_ptr), then the out-pairs (out_ptr / out_epos); all sums have
+ *   a fixed order, no atomics.  `training` as in the forward.  pairs >= 1.
+ * i3d_mse_fwd: loss[0] = scale * sum_i (a[i] - b[i])^2 (scale = weight / n for torch.nn.MSELoss times the reference's
+ *   reconstruction_reg, commons/losses.py:204) through `partial` (i3d_mse_partial_floats(n) floats): differences, squares and
+ *   sums in fp64, blocks summed in order, rounded once.
+ * i3d_mse_bwd: grad_a[i] = 2 scale g (a[i] - b[i]), grad_b = -grad_a (either may be null), g = grad_scale[0] read on the
+ *   device (null: 1). */
+int i3d_pair_mlp_supported(int width);
+long i3d_pair_mlp_workspace_floats(int pairs, int width);
+int i3d_pair_mlp_fwd(const float* AB, const float* b1, const float* gamma, const float* beta, const float* w2, const float* b2,
+                     const int* src_s, const int* dst_s, const int* perm, int pairs, int width, int training, float eps,
+                     float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, double* stats,
+                     double* coef, float* workspace, float* out, void* stream);
+int i3d_pair_mlp_bwd(const float* grad_out, const double* coef, const float* AB, const float* b1, const float* gamma,
+                     const float* beta, const float* w2, const int* src_s, const int* dst_s, const int* perm, const int* in_ptr,
+                     const int* out_ptr, const int* out_epos, int num_nodes, int pairs, int width, int training,
+                     const double* stats, float* workspace, float* grad_pair, double* bcoef, float* grad_AB, float* grad_gamma,
+                     float* grad_beta, float* grad_w2, float* grad_b2, void* stream);
+long i3d_mse_partial_floats(long n);
+int i3d_mse_fwd(const float* a, const float* b, long n, double scale, float* partial, float* loss, void* stream);
+int i3d_mse_bwd(const float* a, const float* b, long n, double scale, const float* grad_scale, float* grad_a, float* grad_b,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
