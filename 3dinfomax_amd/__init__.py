@@ -27,7 +27,7 @@ def __getattr__(name):
     if name == 'Net3DAE':
         from . import net3d_ae
         return net3d_ae.Net3DAE
-    if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE'):
+    if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -61,4 +61,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'conformer_collate', 'graph_collate', 's_norm_graph_collate', 's_norm_contrastive_collate', 'BatchedMolGraph', 'batch', 'bond_graph', 'complete_graph', 'Adam', 'PositiveSimilarity',
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
            'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate',
-           'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate']
+           'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate', 'NTXentMultiplePositivesSeparate2D',
+           'NTXentMMDSeparate2D']

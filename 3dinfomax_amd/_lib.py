@@ -341,6 +341,13 @@ _SIGNATURES = {
     'i3d_mse_bwd': (c_int, [_P, _P, c_long, c_double, _P, _P, _P, _P]),
     'i3d_node_drop_build': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                     POINTER(NodeDropView), c_int, _P]),
+    'i3d_row_normalize_fwd': (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    'i3d_row_normalize_bwd': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
+    'i3d_sep2d_max_conformers': (c_int, []),
+    'i3d_sep2d_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P]),
+    'i3d_sep2d_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
+    'i3d_mmd_pair_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P]),
+    'i3d_mmd_pair_bwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, c_double] + [_P] * 5),
 }
 
 _lib = None

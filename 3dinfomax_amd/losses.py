@@ -323,3 +323,150 @@ class NTXentAE(_NTXentBase):
                                           'the pairs of the global batch, which needs the global pair count')
         loss = self._regularisers(self._contrastive(z1, z2, 1), z1, z2)
         return loss, _MSEFn.apply(distances, distance_pred, self.reconstruction_reg)
+
+
+# ---- one 2D embedding per conformer (csrc/sep2d.hip) ---------------------------------------------------------------------------------
+def _separate2d_shapes(name, z1, z2):
+    """(B, C, D) of z1 [B, C D] and z2 [B C, D]; everything that cannot be viewed that way is refused before any device work"""
+    if z1.dim() != 2 or z2.dim() != 2:
+        raise ValueError(f'{name}: z1 [batch, conformers * dim] and z2 [batch * conformers, dim] expected, got '
+                         f'{tuple(z1.shape)} and {tuple(z2.shape)}')
+    B, D = z1.shape[0], z2.shape[1]
+    if B < 1 or z2.shape[0] % B != 0:
+        raise ValueError(f'{name}: the {z2.shape[0]} rows of z2 are not a multiple of the batch size {B}')
+    C = z2.shape[0] // B
+    if z1.shape[1] != C * D:
+        raise ValueError(f'{name}: z1 has {z1.shape[1]} columns, {C} conformers of dimension {D} need {C * D}')
+    if C < 1 or C > ops.SEP2D_MAX_CONFORMERS:
+        raise NotImplementedError(f'{name}: {C} conformers per molecule, the kernels are built for 1..{ops.SEP2D_MAX_CONFORMERS}')
+    if B < 2:
+        raise ValueError(f'{name}: a batch of {B} has no negatives')
+    if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {z1.dtype} and {z2.dtype}')
+    return B, C, D
+
+
+class _RowNormalizeFn(torch.autograd.Function):
+    """F.normalize(x, dim=1) of a [rows, dim] matrix, 1e-12 clamp included"""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        y, n = ops.row_normalize_fwd(x)
+        ctx.save_for_backward(x, n)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, n = ctx.saved_tensors
+        return ops.row_normalize_bwd(x, n, grad_y.contiguous())
+
+
+class _Separate2DFn(torch.autograd.Function):
+    """-mean_i log(pos_i / den_i) from the [B C, B C] similarity of the conformer-wise 2D embeddings z1v and the 3D embeddings z2"""
+
+    @staticmethod
+    def forward(ctx, z1v, z2, batch, conf, tau, norm):
+        z1v, z2 = z1v.contiguous(), z2.contiguous()
+        if norm:
+            n1, n2 = ops.row_norms(z1v), ops.row_norms(z2)
+        else:
+            n1 = n2 = torch.ones(z1v.shape[0], dtype=torch.float32, device=z1v.device)
+        sim = ops.gemm(z1v, z2, trans_b=True)
+        row_den, row_pos, loss = ops.sep2d_fwd(sim, n1, n2, batch, conf, tau)
+        ctx.cfg = (batch, conf, tau, norm)
+        ctx.save_for_backward(z1v, z2, n1, n2, sim, row_den, row_pos)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, tau, norm = ctx.cfg
+        z1v, z2, n1, n2, sim, row_den, row_pos = ctx.saved_tensors
+        dsim, ca, cb = ops.sep2d_bwd(sim, n1, n2, row_den, row_pos, batch, conf, tau, grad_out.contiguous().float())
+        dz1 = ops.gemm(dsim, z2)
+        dz2 = ops.gemm(dsim, z1v, trans_a=True)
+        if norm:
+            ops.row_axpy(z1v, ca, dz1)
+            ops.row_axpy(z2, cb, dz2)
+        return dz1, dz2, None, None, None, None
+
+
+class _MMDNTXentFn(torch.autograd.Function):
+    """NT-Xent over sim[a, b] = 1 / (mmd(conformers of x[b], conformers of y[a]) + 1); x the 2D view, y the 3D view, both [B C, D].
+    The kernel bandwidths are constants of the backward pass, as in the reference (computed from .data)."""
+
+    @staticmethod
+    def forward(ctx, x, y, batch, conf, tau, kernel_num, kernel_mul):
+        x, y = x.contiguous(), y.contiguous()
+        sim, bandwidth, cross, intra = ops.mmd_pair_fwd(x, y, batch, conf, kernel_num, kernel_mul)
+        ones = torch.ones(batch, dtype=torch.float32, device=x.device)
+        row_sum, row_pos, loss = ops.ntxent_fwd(sim, ones, ones, batch, batch, 1, 0, tau, 0.0, 1.0 / batch)
+        ctx.cfg = (batch, conf, tau, kernel_num, kernel_mul)
+        ctx.save_for_backward(x, y, sim, bandwidth, cross, intra, ones, row_sum, row_pos)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, tau, kernel_num, kernel_mul = ctx.cfg
+        x, y, sim, bandwidth, cross, intra, ones, row_sum, row_pos = ctx.saved_tensors
+        dsim, _, _ = ops.ntxent_bwd(sim, ones, ones, row_sum, row_pos, batch, batch, 1, 0, tau, 0.0, 1.0 / batch,
+                                    grad_out.contiguous().float())
+        dx, dy = ops.mmd_pair_bwd(x, y, cross, intra, bandwidth, sim, dsim, batch, conf, kernel_num, kernel_mul)
+        return dx, dy, None, None, None, None, None
+
+
+class _Separate2DBase(_NTXentBase):
+    def _refuse_unsupported(self):
+        """before any device work: the data-parallel form, and the regularisers the reference itself cannot apply - it hands them the
+        [B, C, D] views, where cov_loss fails to unpack a 2-D shape and the torch.pdist of uniformity_loss takes 2-D input only"""
+        name = type(self).__name__
+        if self.group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(self.group) > 1:
+                raise NotImplementedError(f'{name} on a process group of more than one rank: the data-parallel form of the '
+                                          'conformer-wise losses is not built')
+        if self.covariance_reg > 0:
+            raise NotImplementedError(f'{name}: covariance_reg > 0 - the reference\'s cov_loss unpacks a 2-D shape and raises on the '
+                                      '[batch, conformers, dim] views this loss hands it')
+        if self.uniformity_reg > 0:
+            raise NotImplementedError(f'{name}: uniformity_reg > 0 - the reference\'s uniformity_loss (torch.pdist) raises on the '
+                                      '[batch, conformers, dim] views this loss hands it')
+
+    def _regularisers(self, loss, z1, z2):
+        """the reference's calls on the [B, C, D] views: std_loss works on them (variance over the batch axis per conformer and
+        feature), the other two are refused"""
+        self._refuse_unsupported()
+        if self.variance_reg > 0:
+            loss = loss + self.variance_reg * (std_loss(z1) + std_loss(z2))
+        return loss
+
+
+class NTXentMultiplePositivesSeparate2D(_Separate2DBase):
+    """reference commons/losses.py:692-744: z1 [B, C D] holds one 2D embedding per conformer, z2 [B C, D] the 3D embeddings, molecule
+    major.  Positives are the matched conformers only; the whole C x C block of the molecule leaves the denominator.  No epsilon."""
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _separate2d_shapes(type(self).__name__, z1, z2)
+        self._refuse_unsupported()
+        loss = _Separate2DFn.apply(z1.reshape(B * C, D), z2, B, C, float(self.tau), bool(self.norm))
+        return self._regularisers(loss, z1.view(B, C, D), z2.view(B, C, D))
+
+
+class NTXentMMDSeparate2D(_Separate2DBase):
+    """reference commons/losses.py:394-476: the similarity of molecules a (3D view, rows) and b (2D view, columns) is
+    1 / (MMD + 1) of their two conformer sets under a sum of kernel_num Gaussian kernels; NT-Xent over that [B, B] matrix."""
+
+    def __init__(self, norm: bool = True, tau: float = 0.5, uniformity_reg=0, variance_reg=0, covariance_reg=0, kernel_num=5,
+                 kernel_mul=2.0) -> None:
+        super().__init__(norm, tau, uniformity_reg, variance_reg, covariance_reg)
+        self.kernel_num, self.kernel_mul = kernel_num, kernel_mul
+        self.fix_sigma = None
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _separate2d_shapes(type(self).__name__, z1, z2)
+        self._refuse_unsupported()
+        x, y = z1.reshape(B * C, D), z2
+        if self.norm:
+            x, y = _RowNormalizeFn.apply(x), _RowNormalizeFn.apply(y)
+        loss = _MMDNTXentFn.apply(x, y, B, C, float(self.tau), int(self.kernel_num), float(self.kernel_mul))
+        return self._regularisers(loss, x.view(B, C, D), y.view(B, C, D))

@@ -961,3 +961,75 @@ def mse_bwd(a, b, scale, grad_scale_dev, need_a=True, need_b=True):
     if need_a or need_b:
         check(_lib.load().i3d_mse_bwd(_p(a), _p(b), n, float(scale), _p(grad_scale_dev), _p(ga), _p(gb), _stream()), 'i3d_mse_bwd')
     return ga, gb
+
+
+# ---- multi-conformer losses with one 2D embedding per conformer (csrc/sep2d.hip) ------------------------------------------------------
+SEP2D_MAX_CONFORMERS = 8
+
+
+def row_normalize_fwd(x):
+    """-> (x / max(|x|, 1e-12) per row, the row norms): torch F.normalize"""
+    _chk(x)
+    y = torch.empty_like(x)
+    n = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    check(_lib.load().i3d_row_normalize_fwd(_p(x), x.shape[0], x.shape[1], _p(y), _p(n), _stream()), 'i3d_row_normalize_fwd')
+    return y, n
+
+
+def row_normalize_bwd(x, norms, grad_y):
+    _chk(x)
+    _chk(grad_y)
+    gx = torch.empty_like(x)
+    check(_lib.load().i3d_row_normalize_bwd(_p(x), _p(norms), _p(grad_y), x.shape[0], x.shape[1], _p(gx), _stream()),
+          'i3d_row_normalize_bwd')
+    return gx
+
+
+def sep2d_fwd(sim, n1, n2, batch, conf, tau):
+    """sim [B C, B C] (rows: 2D view, columns: 3D view) -> (row_den [B], row_pos [B], both fp64, loss [1])"""
+    _chk(sim)
+    row_den = torch.empty(batch, dtype=torch.float64, device=sim.device)
+    row_pos = torch.empty(batch, dtype=torch.float64, device=sim.device)
+    loss = torch.empty(1, dtype=torch.float32, device=sim.device)
+    check(_lib.load().i3d_sep2d_fwd(_p(sim), _p(n1), _p(n2), batch, conf, float(tau), _p(row_den), _p(row_pos), _p(loss), _stream()),
+          'i3d_sep2d_fwd')
+    return row_den, row_pos, loss
+
+
+def sep2d_bwd(sim, n1, n2, row_den, row_pos, batch, conf, tau, grad_scale_dev):
+    """-> (dsim, ca [B C], cb [B C]); the upstream scalar gradient grad_scale_dev[0] is multiplied in on the device"""
+    dsim = torch.empty_like(sim)
+    ca = torch.empty(batch * conf, dtype=torch.float32, device=sim.device)
+    cb = torch.empty(batch * conf, dtype=torch.float32, device=sim.device)
+    check(_lib.load().i3d_sep2d_bwd(_p(sim), _p(n1), _p(n2), _p(row_den), _p(row_pos), batch, conf, float(tau), _p(grad_scale_dev),
+                                    _p(dsim), _p(ca), _p(cb), _stream()), 'i3d_sep2d_bwd')
+    return dsim, ca, cb
+
+
+def mmd_pair_fwd(X, Y, batch, conf, kernel_num, kernel_mul):
+    """X (2D view), Y (3D view) [B C, D] -> (sim [B, B], bandwidth [B, B], cross [B C, B C], intra [2, B, C, C]); entry [a, b]
+    compares the conformers of X[b] with those of Y[a]"""
+    _chk(X)
+    _chk(Y)
+    N, D = X.shape
+    dev = X.device
+    cross = torch.empty(N, N, dtype=torch.float32, device=dev)
+    intra = torch.empty(2, batch, conf, conf, dtype=torch.float32, device=dev)
+    bandwidth = torch.empty(batch, batch, dtype=torch.float32, device=dev)
+    sim = torch.empty(batch, batch, dtype=torch.float32, device=dev)
+    check(_lib.load().i3d_mmd_pair_fwd(_p(X), _p(Y), batch, conf, D, int(kernel_num), float(kernel_mul), _p(cross), _p(intra),
+                                       _p(bandwidth), _p(sim), _stream()), 'i3d_mmd_pair_fwd')
+    return sim, bandwidth, cross, intra
+
+
+def mmd_pair_bwd(X, Y, cross, intra, bandwidth, sim, dsim, batch, conf, kernel_num, kernel_mul):
+    """-> (dX, dY) from dsim [B, B]; the bandwidth is a constant"""
+    _chk(dsim)
+    N, D = X.shape
+    gcross = torch.empty_like(cross)
+    gintra = torch.empty_like(intra)
+    dX, dY = torch.empty_like(X), torch.empty_like(Y)
+    check(_lib.load().i3d_mmd_pair_bwd(_p(X), _p(Y), _p(cross), _p(intra), _p(bandwidth), _p(sim), _p(dsim), batch, conf, D,
+                                       int(kernel_num), float(kernel_mul), _p(gcross), _p(gintra), _p(dX), _p(dY), _stream()),
+          'i3d_mmd_pair_bwd')
+    return dX, dY

@@ -1174,6 +1174,36 @@ int i3d_mse_fwd(const float* a, const float* b, long n, double scale, float* par
 int i3d_mse_bwd(const float* a, const float* b, long n, double scale, const float* grad_scale, float* grad_a, float* grad_b,
                 void* stream);
 
+/* ---- multi-conformer losses with one 2D embedding per conformer (reference commons/losses.py:394-476, 692-744; csrc/sep2d.hip) ----
+ * B = batch molecules, C = conf conformers (1..i3d_sep2d_max_conformers() = 8), N = B C points per view, D = dim features.  Both
+ * views are [N, D], molecule major.  Every sum has a fixed order, no atomics; nothing of size B^2 C^2 D exists.
+ * i3d_row_normalize_fwd: y = x / max(|x|, 1e-12) per row (torch F.normalize), norms[r] = |x_r| (before the clamp).
+ * i3d_row_normalize_bwd: grad_x = (grad_y - y (y . grad_y)) / |x|; rows below the clamp: grad_y / 1e-12.
+ * i3d_sep2d_fwd: sim [N, N] = z1v z2^T (rows (i, l), columns (j, u)), n1 / n2 [N] the row norms (ones: no normalisation), no
+ *   epsilon.  P = exp(sim / (n1 n2) / tau); row_den[i] = sum of P over the rows of molecule i and the columns of every OTHER
+ *   molecule, row_pos[i] = sum_l P[(i, l), (i, l)] (fp64, [B]); loss[0] = -mean_i log(row_pos / row_den).
+ * i3d_sep2d_bwd: dsim = dL/d sim [N, N] and the norm-path coefficients ca, cb [N] (dz1 = dsim z2 + ca z1v, dz2 = dsim^T z1v +
+ *   cb z2), times grad_scale[0] read on the device (null: 1).
+ * i3d_mmd_pair_fwd: X = the 2D view, Y = the 3D view (normalised by the caller).  Entry [a, b] of sim / bandwidth [B, B] compares
+ *   the 2C points X[b] followed by Y[a]: cross [N, N] with cross[(a, u), (b, l)] = |Y[a, u] - X[b, l]|^2 and intra [2, B, C, C]
+ *   (0: X, 1: Y) by direct differences; bandwidth = (sum of all (2C)^2 squared distances) / ((2C)^2 - 2C) / kernel_mul^(kernel_num / 2);
+ *   K(L) = sum_{k < kernel_num} exp(-L / (bandwidth kernel_mul^k)); mmd = mean over C x C of K_XX + K_YY - K_XY - K_YX;
+ *   sim = 1 / (mmd + 1).  cross, intra, bandwidth and sim are outputs, and inputs of the backward pass.
+ * i3d_mmd_pair_bwd: from dsim [B, B], with the bandwidth held constant: dX, dY [N, D].  gcross [N, N] and gintra [2, B, C, C] are
+ *   scratch. */
+int i3d_row_normalize_fwd(const float* x, int rows, int dim, float* y, float* norms, void* stream);
+int i3d_row_normalize_bwd(const float* x, const float* norms, const float* grad_y, int rows, int dim, float* grad_x, void* stream);
+int i3d_sep2d_max_conformers(void);
+int i3d_sep2d_fwd(const float* sim, const float* n1, const float* n2, int batch, int conf, float tau, double* row_den,
+                  double* row_pos, float* loss, void* stream);
+int i3d_sep2d_bwd(const float* sim, const float* n1, const float* n2, const double* row_den, const double* row_pos, int batch,
+                  int conf, float tau, const float* grad_scale, float* dsim, float* ca, float* cb, void* stream);
+int i3d_mmd_pair_fwd(const float* X, const float* Y, int batch, int conf, int dim, int kernel_num, double kernel_mul, float* cross,
+                     float* intra, float* bandwidth, float* sim, void* stream);
+int i3d_mmd_pair_bwd(const float* X, const float* Y, const float* cross, const float* intra, const float* bandwidth,
+                     const float* sim, const float* dsim, int batch, int conf, int dim, int kernel_num, double kernel_mul,
+                     float* gcross, float* gintra, float* dX, float* dY, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
