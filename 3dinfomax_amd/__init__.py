@@ -27,7 +27,8 @@ def __getattr__(name):
     if name == 'Net3DAE':
         from . import net3d_ae
         return net3d_ae.Net3DAE
-    if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D'):
+    if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
+                'KLDivergenceMultiplePositives'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -40,7 +41,8 @@ def __getattr__(name):
         from . import mol_encoder
         return getattr(mol_encoder, name)
     if name in ('PositiveSimilarity', 'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate',
-                'Uniformity', 'Alignment', 'BatchVariance', 'DimensionCovariance', 'contrastive_metrics'):
+                'Uniformity', 'Alignment', 'BatchVariance', 'DimensionCovariance', 'Conformer3DVariance', 'Conformer2DVariance',
+                'contrastive_metrics'):
         from . import metrics
         return getattr(metrics, name)
     if name == 'Adam':
@@ -62,4 +64,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
            'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate',
            'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate', 'NTXentMultiplePositivesSeparate2D',
-           'NTXentMMDSeparate2D']
+           'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance']

@@ -348,6 +348,8 @@ _SIGNATURES = {
     'i3d_sep2d_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
     'i3d_mmd_pair_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P]),
     'i3d_mmd_pair_bwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, c_double] + [_P] * 5),
+    'i3d_kl_mp_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P]),
+    'i3d_kl_mp_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -123,6 +123,17 @@ __device__ __forceinline__ float act_grad_any(float x, int act) {
 // the fused kernels' activation codes (see above)
 inline bool fused_act(int act) { return act >= I3D_ACT_NONE && act <= I3D_ACT_LEAKY_RELU; }
 
+// (sep2d.hip, klmp.hip) sum of v over the 256 threads of the workgroup through sm, four doubles of LDS; the same order every time:
+// lanes by a butterfly, then the four waves in order
+__device__ __forceinline__ double block_sum_f64(double v, double* sm) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sm[w] = v;
+    __syncthreads();
+    return ((sm[0] + sm[1]) + sm[2]) + sm[3];
+}
+
 // aggregate.hip: the next K4 forward launch of this thread carries these timing events (bench.py's in-step roofline figure)
 void k4_time_next_launch(void* start, void* stop);
 

@@ -26,16 +26,6 @@ namespace i3d {
 constexpr int S2_MAX_CONF = 8;
 constexpr double S2_NORM_EPS = 1e-12;
 
-// sum of v over the 256 threads of the workgroup, the same order every time: lanes by a butterfly, then the four waves in order
-__device__ __forceinline__ double s2_block_sum(double v, double* sm) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sm[w] = v;
-    __syncthreads();
-    return ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
-
 // ---- row normalise ------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 row_normalize_fwd_kernel(const float* __restrict__ x, int rows, int dim, float* __restrict__ y, float* __restrict__ norms) {
@@ -95,8 +85,8 @@ sep2d_fwd_kernel(const float* __restrict__ sim, const float* __restrict__ n1, co
             else den += p;
         }
     }
-    den = s2_block_sum(den, sm);
-    pos = s2_block_sum(pos, sm);
+    den = block_sum_f64(den, sm);
+    pos = block_sum_f64(pos, sm);
     if (threadIdx.x == 0) {
         row_den[i] = den;
         row_pos[i] = pos;
@@ -109,7 +99,7 @@ sep2d_loss_kernel(const double* __restrict__ row_den, const double* __restrict__
     __shared__ double sm[4];
     double acc = 0.;
     for (int i = threadIdx.x; i < B; i += 256) acc -= log(row_pos[i] / row_den[i]);
-    acc = s2_block_sum(acc, sm);
+    acc = block_sum_f64(acc, sm);
     if (threadIdx.x == 0) loss[0] = (float)(acc / (double)B);
 }
 
@@ -141,7 +131,7 @@ sep2d_bwd_row_kernel(const float* __restrict__ sim, const float* __restrict__ n1
         }
         dsim[r * N + c] = h;
     }
-    da = s2_block_sum(da, sm);
+    da = block_sum_f64(da, sm);
     if (threadIdx.x == 0) ca[r] = a > 0. ? (float)(da / a) : 0.f;
 }
 
@@ -330,7 +320,7 @@ mmd_intra_bwd_kernel(const float* __restrict__ intra, const float* __restrict__ 
                 const double s = (double)sim[idx];
                 acc += -(double)dsim[idx] * s * s * mmd_kernel_dsum(L, (double)bandwidth[idx], mul, num);
             }
-            acc = s2_block_sum(acc, sm);
+            acc = block_sum_f64(acc, sm);
             if (threadIdx.x == 0) {
                 const float g = (float)(acc * 2. / (double)CC);
                 gintra[base + l * C + l2] = g;

@@ -221,15 +221,20 @@ class _NTXentBase(_Loss):
             raise ValueError(f'ranks hold different numbers of molecules ({rows} here, {int(-float(n[1]))}..'
                              f'{int(float(n[0]))} over the group): pass them with loss.set_shard_counts(dist.shard_counts(...))')
 
+    def _valid_shard_counts(self, rows, world, rank):
+        """the counts of set_shard_counts (None: equal shards), refused when they do not describe this rank's batch"""
+        counts = self.shard_counts
+        if counts is not None and (len(counts) != world or counts[rank] != rows):
+            raise ValueError(f'shard counts {counts} do not describe this batch ({rows} rows on rank {rank})')
+        return counts
+
     def _contrastive(self, z1, z2, conf):
         pos_offset, global_batch = 0, z1.shape[0]
         if self.group is not None:
             import torch.distributed as dist
             world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
             if world > 1:
-                counts = self.shard_counts
-                if counts is not None and (len(counts) != world or counts[rank] != z1.shape[0]):
-                    raise ValueError(f'shard counts {counts} do not describe this batch ({z1.shape[0]} rows on rank {rank})')
+                counts = self._valid_shard_counts(z1.shape[0], world, rank)
                 if counts is not None and max(counts) != min(counts):
                     z2 = _AllGatherRowsFn.apply(z2, self.group, [c * conf for c in counts])
                     pos_offset, global_batch = sum(counts[:rank]), sum(counts)
@@ -416,25 +421,28 @@ class _MMDNTXentFn(torch.autograd.Function):
 
 
 class _Separate2DBase(_NTXentBase):
+    _data_parallel = False          # True: the class has a data-parallel form of its own
+
     def _refuse_unsupported(self):
-        """before any device work: the data-parallel form, and the regularisers the reference itself cannot apply - it hands them the
-        [B, C, D] views, where cov_loss fails to unpack a 2-D shape and the torch.pdist of uniformity_loss takes 2-D input only"""
+        """before any device work: the data-parallel form (where the class has none), and the regularisers the reference itself cannot
+        apply - it hands them the 3-D views, where cov_loss fails to unpack a 2-D shape and the torch.pdist of uniformity_loss takes
+        2-D input only"""
         name = type(self).__name__
-        if self.group is not None:
+        if not self._data_parallel and self.group is not None:
             import torch.distributed as dist
             if dist.get_world_size(self.group) > 1:
                 raise NotImplementedError(f'{name} on a process group of more than one rank: the data-parallel form of the '
                                           'conformer-wise losses is not built')
         if self.covariance_reg > 0:
             raise NotImplementedError(f'{name}: covariance_reg > 0 - the reference\'s cov_loss unpacks a 2-D shape and raises on the '
-                                      '[batch, conformers, dim] views this loss hands it')
+                                      '3-D views this loss hands it')
         if self.uniformity_reg > 0:
             raise NotImplementedError(f'{name}: uniformity_reg > 0 - the reference\'s uniformity_loss (torch.pdist) raises on the '
-                                      '[batch, conformers, dim] views this loss hands it')
+                                      '3-D views this loss hands it')
 
     def _regularisers(self, loss, z1, z2):
-        """the reference's calls on the [B, C, D] views: std_loss works on them (variance over the batch axis per conformer and
-        feature), the other two are refused"""
+        """the reference's calls on the 3-D views: std_loss works on them (variance over the batch axis per conformer and feature),
+        the other two are refused"""
         self._refuse_unsupported()
         if self.variance_reg > 0:
             loss = loss + self.variance_reg * (std_loss(z1) + std_loss(z2))
@@ -470,3 +478,77 @@ class NTXentMMDSeparate2D(_Separate2DBase):
             x, y = _RowNormalizeFn.apply(x), _RowNormalizeFn.apply(y)
         loss = _MMDNTXentFn.apply(x, y, B, C, float(self.tau), int(self.kernel_num), float(self.kernel_mul))
         return self._regularisers(loss, x.view(B, C, D), y.view(B, C, D))
+
+
+# ---- the conformers as one diagonal Gaussian per molecule (csrc/klmp.hip) --------------------------------------------------------------
+def _kl_shapes(name, z1, z2):
+    """(B, C, D) of z1 [B, 2 D] (mean | log-variance) and z2 [B C, D]; everything else is refused before any device work"""
+    if z1.dim() != 2 or z2.dim() != 2:
+        raise ValueError(f'{name}: z1 [batch, 2 * dim] and z2 [batch * conformers, dim] expected, got {tuple(z1.shape)} and '
+                         f'{tuple(z2.shape)}')
+    B, D = z1.shape[0], z2.shape[1]
+    if D < 1 or z1.shape[1] != 2 * D:
+        raise ValueError(f'{name}: z1 has {z1.shape[1]} columns, a mean and a log-variance of dimension {D} need {2 * D}')
+    if B < 1 or z2.shape[0] % B != 0:
+        raise ValueError(f'{name}: the {z2.shape[0]} rows of z2 are not a multiple of the batch size {B}')
+    C = z2.shape[0] // B
+    if C < 2:
+        raise ValueError(f'{name}: {C} conformer(s) per molecule - the variance over the conformers needs at least two')
+    if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {z1.dtype} and {z2.dtype}')
+    return B, C, D
+
+
+class _KLMultiplePositivesFn(torch.autograd.Function):
+    """sum_b KL(N(m2_b, v2_b) || N(m1_b, exp(s1_b))) / global_batch over the local molecules; the backward pass recomputes the conformer
+    statistics instead of keeping them"""
+
+    @staticmethod
+    def forward(ctx, z1, z2, batch, conf, global_batch):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        _, loss = ops.kl_mp_fwd(z1, z2, batch, conf, 1.0 / global_batch)
+        ctx.cfg = (batch, conf, global_batch)
+        ctx.save_for_backward(z1, z2)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, global_batch = ctx.cfg
+        z1, z2 = ctx.saved_tensors
+        dz1, dz2 = ops.kl_mp_bwd(z1, z2, batch, conf, 1.0 / global_batch, grad_out.contiguous().float())
+        return dz1, dz2, None, None, None
+
+
+class KLDivergenceMultiplePositives(_Separate2DBase):
+    """reference commons/losses.py:261-314: z1 [B, 2 D] holds a mean and a log-variance per molecule, z2 [B C, D] the 3D embeddings of
+    its C conformers, molecule major; the loss is the mean over the molecules of KL(N(mean_c z2, var_c z2 + 1e-6) || N(mean, exp(log-
+    variance))).  No normalisation by default; `tau` is accepted and unused, as in the reference.  There are no negatives, so a batch of
+    one is valid and the data-parallel form needs no gather: on a group of more than one rank the value is this rank's share
+    sum_local kl_b / B_global (the convention of NTXent)."""
+    _data_parallel = True
+
+    def __init__(self, norm: bool = False, tau: float = 0.5, uniformity_reg=0, variance_reg=0, covariance_reg=0) -> None:
+        super().__init__(norm, tau, uniformity_reg, variance_reg, covariance_reg)
+
+    def _global_batch(self, z1):
+        if self.group is None:
+            return z1.shape[0]
+        import torch.distributed as dist
+        world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        if world == 1:
+            return z1.shape[0]
+        counts = self._valid_shard_counts(z1.shape[0], world, rank)
+        if counts is not None:
+            return sum(counts)
+        self._check_equal_shards(z1, dist)
+        return world * z1.shape[0]
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _kl_shapes(type(self).__name__, z1, z2)
+        self._refuse_unsupported()
+        global_batch = self._global_batch(z1)
+        a, b = z1.reshape(2 * B, D), z2
+        if self.norm:
+            a, b = _RowNormalizeFn.apply(a), _RowNormalizeFn.apply(b)
+        loss = _KLMultiplePositivesFn.apply(a.reshape(B, 2 * D), b, B, C, global_batch)
+        return self._regularisers(loss, a.view(B, 2, D), b.view(B, C, D))

@@ -8,6 +8,10 @@ Here the first metric asked about a pair of embedding tensors computes ALL of th
 find the result cached, so the trainer's loop costs one synchronisation.  Same class names, constructor arguments and
 call signature; the value comes back as a 0-dim CPU tensor (`.item()` works as in the trainer).  The `pos_mask`
 (local-global losses) variants are outside the scope of this path and raise NotImplementedError.
+
+The metrics of configs/contrastive_training_multiple_positives_kl_div_loss.yml see z1 [B, 2 D] and z2 [B C, D]: Conformer3DVariance /
+Conformer2DVariance (reference trainer/metrics.py:177-209) share one pass of the KL loss's forward kernel, BatchVariance and
+DimensionCovariance - one term per tensor - the per-tensor part of the pass above; each pair costs one synchronisation.
 """
 import math
 import weakref
@@ -34,11 +38,41 @@ def _log(v):
         return float(np.log(v))
 
 
+def _tensor_key(x1, x2, *extra):
+    return (x1.data_ptr(), x1._version, tuple(x1.shape), x2.data_ptr(), x2._version, tuple(x2.shape)) + extra
+
+
+def _cached(cache, key, x1, x2):
+    if cache['key'] == key and _same_object(cache['x1'], x1) and _same_object(cache['x2'], x2):
+        return cache['values']
+    return None
+
+
+def _fill(cache, key, x1, x2, vals):
+    cache['key'], cache['values'] = key, vals
+    cache['x1'], cache['x2'] = weakref.ref(x1), weakref.ref(x2)
+    return vals
+
+
+def _second_moments(L, z, n):
+    """device parts of one [n, D] tensor: [sum of the squared off-diagonal covariances], column sums [D], column sums of squares [D]"""
+    D = z.shape[1]
+    C = ops.gemm(z, z, trans_a=True)               # [D, D] second moments
+    s = ops.colsum(z)
+    cr = torch.empty(D, 2, dtype=torch.float32, device=z.device)
+    _lib.check(L.i3d_cov_rowstats(C.data_ptr(), s.data_ptr(), n, D, cr.data_ptr(), ops._stream()), 'i3d_cov_rowstats')
+    return [ops.colsum(cr)[:1], s, cr[:, 1].contiguous()]
+
+
+def _col_std_mean(s, q, n):
+    return float(np.sqrt(np.maximum(q - s * s / n, 0.0) / max(n - 1, 1)).mean())
+
+
 def _all_metrics(x1, x2, threshold=0.5, t=2.0, alpha=2.0):
-    key = (x1.data_ptr(), x1._version, tuple(x1.shape), x2.data_ptr(), x2._version, tuple(x2.shape), float(threshold), float(t),
-           float(alpha))
-    if _cache['key'] == key and _same_object(_cache['x1'], x1) and _same_object(_cache['x2'], x2):
-        return _cache['values']
+    key = _tensor_key(x1, x2, float(threshold), float(t), float(alpha))
+    vals = _cached(_cache, key, x1, x2)
+    if vals is not None:
+        return vals
     with torch.no_grad():
         z1, z2 = x1.detach().float().contiguous(), x2.detach().float().contiguous()
         if not z1.is_cuda:
@@ -56,20 +90,13 @@ def _all_metrics(x1, x2, threshold=0.5, t=2.0, alpha=2.0):
                                               float(alpha), rows.data_ptr(), ops._stream()), 'i3d_contrastive_rowstats')
         parts = [ops.colsum(rows)]
         for z, n in ((z1, B1), (z2, B2)):
-            C = ops.gemm(z, z, trans_a=True)               # [D, D] second moments
-            s = ops.colsum(z)
-            cr = torch.empty(D, 2, dtype=torch.float32, device=z.device)
-            _lib.check(L.i3d_cov_rowstats(C.data_ptr(), s.data_ptr(), n, D, cr.data_ptr(), ops._stream()), 'i3d_cov_rowstats')
-            parts += [ops.colsum(cr)[:1], s, cr[:, 1].contiguous()]
+            parts += _second_moments(L, z, n)
         host = torch.cat([p.reshape(-1) for p in parts]).cpu().double().numpy()     # the one device-to-host copy
     r = host[:8]
     o = 8
     cov1, s1, q1 = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
     o += 1 + 2 * D
     cov2, s2, q2 = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
-
-    def col_std_mean(s, q, n):
-        return float(np.sqrt(np.maximum(q - s * s / n, 0.0) / max(n - 1, 1)).mean())
 
     def all_mean_std(s, q, n):
         cnt = n * D
@@ -84,14 +111,69 @@ def _all_metrics(x1, x2, threshold=0.5, t=2.0, alpha=2.0):
         'true_positive_rate': tpr, 'true_negative_rate': tnr, 'contrastive_accuracy': (tpr + tnr) / 2,
         'alignment': r[4] / B1,
         'uniformity': (_log(r[5] / (B1 * (B1 - 1) / 2)) + _log(r[6] / (B2 * (B2 - 1) / 2))) / 2 if B1 > 1 else float('nan'),
-        'batch_variance': col_std_mean(s1, q1, B1) + col_std_mean(s2, q2, B2),
+        'batch_variance': _col_std_mean(s1, q1, B1) + _col_std_mean(s2, q2, B2),
         'dimension_covariance': cov1 / D + cov2 / D,
     }
     vals['mean_pred'], vals['std_pred'] = all_mean_std(s1, q1, B1)
     vals['mean_targets'], vals['std_targets'] = all_mean_std(s2, q2, B2)
-    _cache['key'], _cache['values'] = key, vals
-    _cache['x1'], _cache['x2'] = weakref.ref(x1), weakref.ref(x2)
-    return vals
+    return _fill(_cache, key, x1, x2, vals)
+
+
+# BatchVariance and DimensionCovariance are sums of one term per tensor: on embeddings of different widths (z1 [B, 2 D] and z2 [B C, D]
+# of KLDivergenceMultiplePositives) they take this pass, the per-tensor part of the one above, with a cache of its own.
+_per_tensor_cache = {'key': None, 'values': None, 'x1': None, 'x2': None}
+
+
+def _per_tensor_metrics(x1, x2):
+    key = _tensor_key(x1, x2)
+    vals = _cached(_per_tensor_cache, key, x1, x2)
+    if vals is not None:
+        return vals
+    with torch.no_grad():
+        zs = [x.detach().float().contiguous() for x in (x1, x2)]
+        if not all(z.is_cuda for z in zs):
+            raise AssertionError('the metrics run on the HIP device (there is no CPU fallback)')
+        if any(z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1 for z in zs):
+            raise ValueError(f'incompatible embedding shapes {tuple(x1.shape)} / {tuple(x2.shape)}')
+        L = _lib.load()
+        parts = [p for z in zs for p in _second_moments(L, z, z.shape[0])]
+        host = torch.cat([p.reshape(-1) for p in parts]).cpu().double().numpy()     # the one device-to-host copy
+    vals, o = {'batch_variance': 0.0, 'dimension_covariance': 0.0}, 0
+    for z in zs:
+        n, D = z.shape
+        cov, s, q = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
+        o += 1 + 2 * D
+        vals['batch_variance'] += _col_std_mean(s, q, n)
+        vals['dimension_covariance'] += cov / D
+    return _fill(_per_tensor_cache, key, x1, x2, vals)
+
+
+# Conformer3DVariance / Conformer2DVariance: the second and third per-molecule sums of the KL loss's forward kernel (csrc/klmp.hip)
+_conformer_cache = {'key': None, 'values': None, 'x1': None, 'x2': None}
+
+
+def _conformer_metrics(x1, x2, normalize):
+    """z1 [B, 2 D] (mean | log-variance), z2 [B C, D]: the mean over molecules and features of the variance over the conformers, and of
+    exp(log-variance); normalize: both on the row-normalised views (F.normalize(dim=2) of [B, 2, D] and [B, C, D])"""
+    key = _tensor_key(x1, x2, bool(normalize))
+    vals = _cached(_conformer_cache, key, x1, x2)
+    if vals is not None:
+        return vals
+    if x1.dim() != 2 or x2.dim() != 2 or x1.shape[0] < 1 or x1.shape[1] != 2 * x2.shape[1] or x2.shape[0] % x1.shape[0] != 0 \
+            or x2.shape[0] // x1.shape[0] < 2:
+        raise ValueError(f'incompatible embedding shapes {tuple(x1.shape)} / {tuple(x2.shape)}: [batch, 2 * dim] and '
+                         '[batch * conformers, dim] with at least two conformers expected')
+    with torch.no_grad():
+        z1, z2 = x1.detach().float().contiguous(), x2.detach().float().contiguous()
+        if not (z1.is_cuda and z2.is_cuda):
+            raise AssertionError('the metrics run on the HIP device (there is no CPU fallback)')
+        B, D = z1.shape[0], z2.shape[1]
+        if normalize:
+            z1, z2 = ops.row_normalize_fwd(z1.reshape(2 * B, D))[0], ops.row_normalize_fwd(z2)[0]
+        stats, _ = ops.kl_mp_fwd(z1, z2, B, z2.shape[0] // B, 1.0 / B, want_loss=False)
+        host = stats.cpu().numpy()                                                  # the one device-to-host copy
+    vals = {'conformer_3d_variance': float(host[:, 1].sum() / (B * D)), 'conformer_2d_variance': float(host[:, 2].sum() / (B * D))}
+    return _fill(_conformer_cache, key, x1, x2, vals)
 
 
 def contrastive_metrics(z2d, z3d, threshold=0.5009, t=2.0, alpha=2.0):
@@ -176,11 +258,41 @@ class Alignment(_Metric):
         return {'alpha': self.alpha}
 
 
-class BatchVariance(_Metric):
+class _PerTensor(_Metric):
+    """a sum of one term per tensor: embeddings of different widths are fine"""
+
+    def forward(self, x1, x2, pos_mask=None):
+        if pos_mask is None and x1.dim() == 2 and x2.dim() == 2 and x1.shape[1] != x2.shape[1]:
+            return torch.tensor(_per_tensor_metrics(x1, x2)[self.name], dtype=torch.float32)
+        return super().forward(x1, x2, pos_mask)
+
+
+class BatchVariance(_PerTensor):
     """reference trainer/metrics.py:169-174."""
     name = 'batch_variance'
 
 
-class DimensionCovariance(_Metric):
+class DimensionCovariance(_PerTensor):
     """reference trainer/metrics.py:161-166, commons/losses.py:954-959."""
     name = 'dimension_covariance'
+
+
+class _ConformerVariance(nn.Module):
+    name = None
+
+    def __init__(self, normalize=False):
+        super().__init__()
+        self.norm = normalize
+
+    def forward(self, z1, z2, pos_mask=None):
+        return torch.tensor(_conformer_metrics(z1, z2, self.norm)[self.name], dtype=torch.float32)
+
+
+class Conformer3DVariance(_ConformerVariance):
+    """reference trainer/metrics.py:177-192: mean over molecules and features of the variance over the conformers of z2."""
+    name = 'conformer_3d_variance'
+
+
+class Conformer2DVariance(_ConformerVariance):
+    """reference trainer/metrics.py:195-209: mean of exp(log-variance), the second half of every row of z1."""
+    name = 'conformer_2d_variance'

@@ -1033,3 +1033,26 @@ def mmd_pair_bwd(X, Y, cross, intra, bandwidth, sim, dsim, batch, conf, kernel_n
                                        int(kernel_num), float(kernel_mul), _p(gcross), _p(gintra), _p(dX), _p(dY), _stream()),
           'i3d_mmd_pair_bwd')
     return dX, dY
+
+
+# ---- KLDivergenceMultiplePositives (csrc/klmp.hip) -------------------------------------------------------------------------------------
+def kl_mp_fwd(z1, z2, batch, conf, inv_global_batch, want_loss=True):
+    """z1 [B, 2 D] (mean | log-variance), z2 [B C, D] -> (stats [B, 3] fp64: kl_b, sum_d var(z2_b), sum_d exp(s1_b); loss [1] =
+    inv_global_batch sum_b kl_b, or None)"""
+    _chk(z1)
+    _chk(z2)
+    stats = torch.empty(batch, 3, dtype=torch.float64, device=z1.device)
+    loss = torch.empty(1, dtype=torch.float32, device=z1.device) if want_loss else None
+    check(_lib.load().i3d_kl_mp_fwd(_p(z1), _p(z2), batch, conf, z2.shape[1], float(inv_global_batch), _p(stats), _p(loss), _stream()),
+          'i3d_kl_mp_fwd')
+    return stats, loss
+
+
+def kl_mp_bwd(z1, z2, batch, conf, inv_global_batch, grad_scale_dev):
+    """-> (dz1, dz2); the upstream scalar gradient grad_scale_dev[0] is multiplied in on the device"""
+    _chk(z1)
+    _chk(z2)
+    dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
+    check(_lib.load().i3d_kl_mp_bwd(_p(z1), _p(z2), batch, conf, z2.shape[1], float(inv_global_batch), _p(grad_scale_dev), _p(dz1),
+                                    _p(dz2), _stream()), 'i3d_kl_mp_bwd')
+    return dz1, dz2

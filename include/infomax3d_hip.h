@@ -1204,6 +1204,20 @@ int i3d_mmd_pair_bwd(const float* X, const float* Y, const float* cross, const f
                      const float* sim, const float* dsim, int batch, int conf, int dim, int kernel_num, double kernel_mul,
                      float* gcross, float* gintra, float* dX, float* dY, void* stream);
 
+/* ---- KLDivergenceMultiplePositives (reference commons/losses.py:261-314; csrc/klmp.hip) ----
+ * z1 [B, 2 D]: per molecule the mean m1 (columns 0..D-1) and the log-variance s1 (columns D..2D-1) of a diagonal Gaussian; z2 [B C, D],
+ * molecule major: m2 = mean over the C conformers, v2 = their unbiased variance (two-pass) + 1e-6.  B = batch >= 1, C = conf >= 2
+ * (no upper limit), D = dim >= 1; anything else returns I3D_ERR_INVALID before a launch.
+ * i3d_kl_mp_fwd: stats [B, 3] (fp64) = per molecule { kl_b = 0.5 sum_d (s1 - log v2 + (v2 + (m2 - m1)^2) exp(-s1) - 1),
+ *   sum_d var(z2_b) (without the 1e-6), sum_d exp(s1_b) }; loss[0] = inv_global_batch sum_b kl_b in a fixed order (loss null: the
+ *   statistics only).
+ * i3d_kl_mp_bwd: recomputes m2 and v2 and writes every entry of dz1 [B, 2 D] and dz2 [B C, D], times inv_global_batch and
+ *   grad_scale[0] read on the device (null: 1).  No atomics, no scratch. */
+int i3d_kl_mp_fwd(const float* z1, const float* z2, int batch, int conf, int dim, double inv_global_batch, double* stats, float* loss,
+                  void* stream);
+int i3d_kl_mp_bwd(const float* z1, const float* z2, int batch, int conf, int dim, double inv_global_batch, const float* grad_scale,
+                  float* dz1, float* dz2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
