@@ -458,7 +458,7 @@ class GradReducer:
     The models' backward passes (tape.ModelFn) deliver their parameter gradients straight into slices of the buffer
     (one multi-tensor copy per model) and autograd stores those slices as `p.grad`, so a step costs one all-reduce
     (20 MB for PNA + Net3D: ring all-reduce over xGMI is per-link bound, one large message beats many small ones)
-    and no copy back.  Gradients that arrive another way (per-block autograd nodes, I3D_FUSED_MODEL=0) are copied in
+    and no copy back.  Gradients that arrive another way (per-block autograd nodes) are copied in
     here and `p.grad` is re-pointed.  (The per-tensor version - 110 x copy_ - cost ~4 ms of host time per step.)"""
 
     def __init__(self, params, group=None):

@@ -11,14 +11,10 @@ import ctypes
 
 import torch
 
-import os
-
 from . import _lib, ops, tape
 from . import layers as _layers
 from .layers import _keeps_pre, _set_workspaces
 
-# I3D_NATIVE_LAYER=0: the layer as four block composites sequenced from Python (pna.PNALayerFn)
-NATIVE_LAYER = True
 _SIMPLE_ACTS = (None, 'relu', 'leakyrelu')
 KEEP_LAST_ARGS = None
 
@@ -61,7 +57,7 @@ class _Arena:
 
 
 def eligible(h, q, index, qmap, plan, params):
-    if not (NATIVE_LAYER and plan.grouped and h.is_cuda and index.num_edges > 0):
+    if not (plan.grouped and h.is_cuda and index.num_edges > 0):
         return False
     n_pre, n_post = len(plan.pre_specs), len(plan.post_specs)
     if n_pre - 1 > 3 or n_post - 1 > 3 or h.shape[1] % 4:

@@ -16,7 +16,6 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops, tape
-from .streams import fork
 
 SUPPORTED_ACTIVATIONS = {'relu', 'silu', 'sigmoid', 'leakyrelu', 'tanh', 'elu', 'selu', 'softplus', 'none'}
 # activations that exist as an elementwise pass only (csrc/common.h: apply_act_any): the fused kernels - GEMM epilogues, statistics /
@@ -241,13 +240,11 @@ class _Tail:
 
 # ------------------------------------------------------------------------------------------------------------------
 # Composite fast path (csrc/composite.hip): one C call enqueues the whole block.  Eligible: BatchNorm in training mode
-# with local statistics.  I3D_COMPOSITE=0 forces the per-kernel path (identical arithmetic, used by the tests to
-# cross-check).
-COMPOSITE = True
-
+# with local statistics, no dropout, an activation the fused kernels carry, tensors on the GPU.  Everything else takes the
+# per-kernel path (identical arithmetic).
 
 def _composite_ok(spec: FCSpec, *tensors):
-    return (COMPOSITE and spec.bn is not None and spec.bn.training and spec.bn.sync_group is None and spec.dropout == 0.0
+    return (spec.bn is not None and spec.bn.training and spec.bn.sync_group is None and spec.dropout == 0.0
             and spec.act not in ELEMENTWISE_ONLY and spec.post_act not in ELEMENTWISE_ONLY
             and all(t is None or t.is_cuda for t in tensors))
 
@@ -333,13 +330,11 @@ class FCFn(torch.autograd.Function):
         grad_pre, gg, gb = _Tail.backward(ctx.saved, grad_y, gamma, beta, ctx.spec)
         gW = tape.grad_like(W) if ctx.needs_input_grad[1] else None
         gbias = tape.grad_for_bias_of(W, W.shape[0]) if ctx.needs_input_grad[2] else None
-        with fork(grad_pre, x) as f:            # weight/bias gradients next to the data gradient (streams.py)
-            if gW is not None:
-                ops.gemm(grad_pre, x, trans_a=True, out=gW)
-            if gbias is not None:
-                ops.colsum(grad_pre, out=gbias)
+        if gW is not None:
+            ops.gemm(grad_pre, x, trans_a=True, out=gW)
+        if gbias is not None:
+            ops.colsum(grad_pre, out=gbias)
         gx = ops.gemm(grad_pre, W) if ctx.needs_input_grad[0] else None
-        f.join()
         return gx, gW, gbias, gg, gb, grad_res, None
 
 
@@ -366,13 +361,11 @@ class Concat2FCFn(torch.autograd.Function):
         grad_pre, gg, gb = _Tail.backward(ctx.saved, grad_y, gamma, beta, ctx.spec)
         gW = tape.grad_like(W)
         gbias = tape.grad_for_bias_of(W, W.shape[0])
-        with fork(grad_pre, a, c) as f:
-            ops.gemm(grad_pre, c, trans_a=True, out=gW[:, Fa:])
-            ops.gemm(grad_pre, a, trans_a=True, out=gW[:, :Fa])
-            ops.colsum(grad_pre, out=gbias)
+        ops.gemm(grad_pre, c, trans_a=True, out=gW[:, Fa:])
+        ops.gemm(grad_pre, a, trans_a=True, out=gW[:, :Fa])
+        ops.colsum(grad_pre, out=gbias)
         gc = ops.gemm(grad_pre, W[:, Fa:])
         ga = ops.gemm(grad_pre, W[:, :Fa])
-        f.join()
         return ga, gc, gW, gbias, gg, gb, grad_res, None
 
 
@@ -545,18 +538,16 @@ class EdgeFCFn(torch.autograd.Function):
         gQ = None
         if qmap is not None:      # dQ[v] = sum of dpre over the edges of category v
             gQ = ops.gemm(qmap.onehot, grad_pre, trans_a=True)[:qmap.rows]
-        with fork(gP, h, grad_pre, q if ctx.has_q else None) as f:
-            if ctx.has_q:
-                ops.gemm(gQ if qmap is not None else grad_pre, q, trans_a=True, out=gW[:, 2 * Fh:])
-            ops.gemm(gP[:, :Fo], h, trans_a=True, out=gW[:, :Fh])
-            ops.gemm(gP[:, Fo:], h, trans_a=True, out=gW[:, Fh:2 * Fh])
-            ops.colsum(grad_pre, out=gbias)
+        if ctx.has_q:
+            ops.gemm(gQ if qmap is not None else grad_pre, q, trans_a=True, out=gW[:, 2 * Fh:])
+        ops.gemm(gP[:, :Fo], h, trans_a=True, out=gW[:, :Fh])
+        ops.gemm(gP[:, Fo:], h, trans_a=True, out=gW[:, Fh:2 * Fh])
+        ops.colsum(grad_pre, out=gbias)
         gq = None
         if ctx.has_q and ctx.needs_input_grad[1]:
             gq = ops.gemm(gQ if qmap is not None else grad_pre, W[:, 2 * Fh:])
         gh = ops.gemm(gP[:, :Fo], W[:, :Fh])
         ops.gemm(gP[:, Fo:], W[:, Fh:2 * Fh], out=gh, accumulate=True)
-        f.join()
         return gh, gq, gW, gbias, gg, gb, None, None, None
 
 
@@ -683,17 +674,6 @@ class MLP(nn.Module):
         x = tape.apply(EdgeFCFn, h, q, W, b, gamma, beta, index, spec, qmap)
         for fc in list(self.fully_connected)[1:]:
             x = fc(x)
-        return x
-
-    def forward_concat2_grouped(self, h, a, index, coef, residual=None):
-        """[h | scaler blocks of a] -> MLP with the degree-combined weights (GroupedConcat2FCFn) for the first layer."""
-        fcs = list(self.fully_connected)
-        fc0 = fcs[0]
-        gamma, beta = fc0.bn_affine()
-        x = tape.apply(GroupedConcat2FCFn, h, a, fc0.linear.weight, fc0.hot()[1], gamma, beta,      # hot()[1]: the bias, or the zero buffer of bias=False
-                                     residual if len(fcs) == 1 else None, index, coef, fc0.spec())
-        for i, fc in enumerate(fcs[1:]):
-            x = fc(x, residual if i == len(fcs) - 2 else None)
         return x
 
     def forward_concat2(self, a, c, residual=None):

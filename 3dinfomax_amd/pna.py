@@ -11,7 +11,6 @@ the hardware:
   * cat([h, agg]) -> posttrans is two accumulating GEMMs (layers.Concat2FCFn), BN + residual fused.
 """
 import math
-import os
 from typing import Callable, Dict, List, Union
 
 import numpy as np
@@ -32,8 +31,6 @@ PNA_AGGREGATORS = {k: v for k, v in ops.AGG.items()}
 PNA_SCALERS = {k: v for k, v in ops.SCALER.items()}
 
 
-# I3D_FUSED_LAYER=0 runs a PNA layer as four autograd nodes (edge FC, FC, aggregate, posttrans) instead of one
-FUSED_LAYER = True
 # I3D_EDGE_TABLE=0 materialises the [E, F] bond embeddings and multiplies them by W_q in every layer (reference shape)
 EDGE_TABLE = True
 
@@ -348,47 +345,30 @@ class PNALayer(nn.Module):
         avg = float(self.avg_d["log"])
         # degree-grouped posttrans; one scaler or an odd width: the reference-shaped path ([N, 12F] aggregate + K = 13F GEMM)
         grouped = len(self.scalers) > 1 and h.shape[1] % 4 == 0
-        if FUSED_LAYER and h.is_cuda:
-            # per call: only the per-degree scaler coefficients depend on the batch (cached on its index: the layers of a
-            # model share them); specs and parameters come from the FC layers' hot caches
-            fcs = self.__dict__.get('_i3d_fcs')
-            mods = (self.pretrans.fully_connected._modules, self.posttrans.fully_connected._modules)
-            if fcs is None or any(len(k) != len(m) or any(m.get(n) is not fc for n, fc in k)
-                                  for k, m in zip(fcs[2], mods)):      # a replaced / added FC layer drops the cache
-                keyed = tuple(tuple(m.items()) for m in mods)
-                fcs = self.__dict__['_i3d_fcs'] = ([fc for _, fc in keyed[0]], [fc for _, fc in keyed[1]], keyed)
-            pre, post = fcs[0], fcs[1]
-            hots = [fc.hot() for fc in pre + post]
-            plan = _LayerPlan()
-            plan.pre_specs, plan.post_specs = [t[4] for t in hots[:len(pre)]], [t[4] for t in hots[len(pre):]]
-            plan.aggregators, plan.avg, plan.grouped, plan.residual = self.aggregators, avg, grouped, self.residual
-            plan.agg_scalers = [ops.SCALER['identity']] if grouped else self.scalers
-            plan.coef = None
-            if grouped:
-                key = (tuple(self.scalers), avg)
-                cache = idx.__dict__.setdefault('_i3d_coef', {})
-                plan.coef = cache.get(key)
-                if plan.coef is None:
-                    plan.coef = cache[key] = [[_scaler_coef(s, D, avg) for s in self.scalers]
-                                              for D, _, _ in idx.degree_groups()[2]]
-            params = [t for hot in hots for t in hot[:4]]
-            h_new = tape.apply(PNALayerFn, h, ef_sorted if has_q else None, idx,
-                                     qmap if has_q else None, plan, *params)
-            g.ndata['feat'] = h_new
-            return h_new
-        # pretransformation (edge MLP on [h_src | h_dst | e_feat]) -> messages, destination-sorted
-        e = self.pretrans.forward_edge(h, ef_sorted if has_q else None, idx, qmap=qmap if has_q else None)
+        # per call: only the per-degree scaler coefficients depend on the batch (cached on its index: the layers of a
+        # model share them); specs and parameters come from the FC layers' hot caches
+        fcs = self.__dict__.get('_i3d_fcs')
+        mods = (self.pretrans.fully_connected._modules, self.posttrans.fully_connected._modules)
+        if fcs is None or any(len(k) != len(m) or any(m.get(n) is not fc for n, fc in k)
+                              for k, m in zip(fcs[2], mods)):      # a replaced / added FC layer drops the cache
+            keyed = tuple(tuple(m.items()) for m in mods)
+            fcs = self.__dict__['_i3d_fcs'] = ([fc for _, fc in keyed[0]], [fc for _, fc in keyed[1]], keyed)
+        pre, post = fcs[0], fcs[1]
+        hots = [fc.hot() for fc in pre + post]
+        plan = _LayerPlan()
+        plan.pre_specs, plan.post_specs = [t[4] for t in hots[:len(pre)]], [t[4] for t in hots[len(pre):]]
+        plan.aggregators, plan.avg, plan.grouped, plan.residual = self.aggregators, avg, grouped, self.residual
+        plan.agg_scalers = [ops.SCALER['identity']] if grouped else self.scalers
+        plan.coef = None
         if grouped:
-            # the scaler blocks are per-node multiples of the aggregator block that depend on the in-degree only:
-            # aggregate once ([N, n_agg*F], identity block) and fold the scalers into per-degree posttrans weights
-            a = tape.apply(AggregateFn, e, idx, self.aggregators, [ops.SCALER['identity']], avg)
-            coef = [[_scaler_coef(s, D, avg) for s in self.scalers] for D, _, _ in idx.degree_groups()[2]]
-            h_new = self.posttrans.forward_concat2_grouped(h, a, idx, coef, residual=h if self.residual else None)
-        else:
-            # reference-shaped path: mean/max/min/std x scalers written as [N, 12F] in one segmented pass, then
-            # post-transformation on [h | agg] (+ residual fused into the last BN)
-            agg = tape.apply(AggregateFn, e, idx, self.aggregators, self.scalers, avg)
-            h_new = self.posttrans.forward_concat2(h, agg, residual=h if self.residual else None)
+            key = (tuple(self.scalers), avg)
+            cache = idx.__dict__.setdefault('_i3d_coef', {})
+            plan.coef = cache.get(key)
+            if plan.coef is None:
+                plan.coef = cache[key] = [[_scaler_coef(s, D, avg) for s in self.scalers]
+                                          for D, _, _ in idx.degree_groups()[2]]
+        params = [t for hot in hots for t in hot[:4]]
+        h_new = tape.apply(PNALayerFn, h, ef_sorted if has_q else None, idx, qmap if has_q else None, plan, *params)
         g.ndata['feat'] = h_new
         return h_new
 

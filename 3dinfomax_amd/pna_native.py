@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from . import _lib, layer_native, ops, streams, tape
+from . import _lib, ops, streams, tape
 
 NATIVE_MODEL = os.environ.get('I3D_NATIVE_MODEL', '1') != '0'
 _SIMPLE = (None, 'relu', 'leakyrelu')
@@ -41,18 +41,18 @@ def _fc_ok(fc, need_bn):
 
 def eligible(module, g):
     """cheap per-call checks; the structural ones are cached on the module"""
-    if not (NATIVE_MODEL and layer_native.NATIVE_LAYER):
+    if not NATIVE_MODEL:
         return False
     # training mode (with or without autograd: the reference's inference.py runs train-mode BatchNorm under no_grad), or
     # eval mode without autograd - the validation pass of trainer/trainer.py:72-78 (BatchNorm with running statistics,
     # forward only: csrc/model.hip I3dPnaModel.training = 0)
     if not module.training and torch.is_grad_enabled():
         return False
-    if tape.active() is not None or not tape.FUSED_MODEL:
+    if tape.active() is not None:
         return False
     from . import layers as _layers
     from . import pna as P
-    if not (P.FUSED_LAYER and P.EDGE_TABLE and _layers.COMPOSITE):      # A/B switches of the tests
+    if not P.EDGE_TABLE:                       # the sequencer reads the bond table only
         return False
     plist = tape._param_list(module)           # a new list object whenever a sub-module / parameter was replaced
     ent = module.__dict__.get('_i3d_native_ok')
@@ -69,7 +69,7 @@ def eligible(module, g):
         bn = fc.batch_norm                       # the per-block path)
         if fc.training != module.training or (bn is not None and bn.training != module.training):
             return False
-    if not _layers.COMPOSITE or (module.training and not _layers._composite_ok(ent[2][0].hot()[4])):
+    if module.training and not _layers._composite_ok(ent[2][0].hot()[4]):
         return False                             # the gate of the block composites (local statistics)
     feat = g.ndata.get('feat')
     ef = g.edata.get('feat')

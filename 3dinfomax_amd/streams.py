@@ -1,24 +1,15 @@
-"""HIP-stream helpers: run independent kernels of one backward node on a second stream.
+"""The side stream the 3D network runs on beside the 2D network (one per thread and device).
 
-At batch 512 most GEMMs of the step launch 130-520 workgroups on a 256-CU chip that could hold >1000 of them, so
-the weight-gradient GEMMs (dW = dY^T X, which nothing downstream of the node depends on) are enqueued on a side
-stream next to the data-gradient GEMMs of the same node and joined before the node returns.  Ordering rules:
-  * the side stream first waits for the main stream (its inputs - grad_pre, saved activations - were produced there);
-  * every tensor the side kernels read is `record_stream`ed so the caching allocator does not recycle it early;
-  * outputs are allocated on the main stream's pool BEFORE switching streams and the main stream waits for the side
-    stream before the node returns, so autograd (AccumulateGrad, the next node) only ever sees completed tensors.
-EXPERIMENTAL, off by default (I3D_OVERLAP=1 enables it) and only wired into the per-kernel (I3D_COMPOSITE=0) backward
-paths: at batch 512 the host's enqueue rate is as much on the critical path as the GPU, where the extra stream
-bookkeeping costs more than the overlap wins.  (A large-batch gradient check that disagreed with it switched on
-turned out to be arg-max routing flipping on near-ties between two summation orders - DESIGN.md section 6 - not a
-race.)
+`note_step_start` (PNA.forward) marks where the caller's stream stood when the step began; `side_stream_for`
+(Net3D.forward) hands out the side stream ordered after that mark and after the batch's own assembly, or None when
+the call pattern is another one.  `invalidate_step` (every model backward) makes an older mark stale.  The why and the
+ordering rules are with NET3D_STREAM below.
 """
 import os
 import threading
 
 import torch
 
-ENABLED = False
 _tls = threading.local()
 
 
@@ -39,36 +30,6 @@ BOUND_THREAD = None
 def side_stream(device):
     """this thread's side stream on `device` (created on first use): the stream the 3D network runs on beside the 2D network"""
     return _side(torch.device(device))
-
-
-class fork:
-    """with fork(t1, t2, ...) as f:  kernels launched inside run on the side stream; `f.join()` (or leaving the
-    `with` and calling join later in the same node) makes the main stream wait for them."""
-
-    def __init__(self, *reads):
-        self.reads = [t for t in reads if t is not None]
-        self.active = ENABLED and len(self.reads) > 0 and self.reads[0].is_cuda
-        self.main = self.side = self.ctx = None
-
-    def __enter__(self):
-        if self.active:
-            self.main = torch.cuda.current_stream()
-            self.side = _side(self.reads[0].device)
-            self.side.wait_stream(self.main)
-            for t in self.reads:
-                t.record_stream(self.side)
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.active:
-            self.ctx.__exit__(*exc)
-        return False
-
-    def join(self):
-        if self.active:
-            self.main.wait_stream(self.side)
 
 
 # ---- the 3D network next to the 2D network ---------------------------------------------------------------------------
@@ -102,15 +63,6 @@ _generation = [0]      # bumped by every model backward pass (any thread): a mar
 def invalidate_step():
     """a backward pass ran: parameters may change before the next forward"""
     _generation[0] += 1
-
-
-def on_side_stream(device):
-    """is this thread's current stream its side stream?"""
-    pool = getattr(_tls, 'pool', None)
-    if not pool:
-        return False
-    s = pool.get(device.index)
-    return s is not None and s.cuda_stream == torch._C._cuda_getCurrentRawStream(device.index)
 
 
 def side_stream_for(graph_event, device):

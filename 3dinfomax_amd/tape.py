@@ -135,40 +135,20 @@ class ModelFn(torch.autograd.Function):
                 tape.release(o)
             ctx.set_materialize_grads(False)
             ctx.tape, ctx.out_id, ctx.params = tape, tuple(id(o) for o in out), params
-            ctx.on_side_stream = out[0].is_cuda and streams.on_side_stream(out[0].device)
             return out
         tape.release(out)
         ctx.tape, ctx.out_id, ctx.params = tape, id(out), params
-        ctx.on_side_stream = out.is_cuda and streams.on_side_stream(out.device)
         return out
 
     @staticmethod
     def backward(ctx, *grads):
         streams.invalidate_step()
-        if isinstance(ctx.out_id, tuple):
-            # several outputs: the helper-thread backward below (ASYNC_SIDE_BACKWARD) is not offered, the pass runs on this thread
+        if isinstance(ctx.out_id, tuple):         # several outputs: one seed per output that received a gradient
             grad = tuple(g.contiguous() if g is not None else None for g in grads)
-            direct = DIRECT_PARAM_GRADS and _plain_leaves(ctx.params)
-            out = _model_backward(ctx, grad, direct)
-            if direct:
-                for p, g in zip(ctx.params, out):
-                    if g is not None:
-                        p.grad = g
-                return (None,) * (2 + len(ctx.params))
-            return (None, None) + tuple(out)
-        grad = grads[0]
+        else:
+            grad = grads[0].contiguous()
         direct = DIRECT_PARAM_GRADS and _plain_leaves(ctx.params)
-        if direct and ASYNC_SIDE_BACKWARD and ctx.on_side_stream:
-            # The model ran next to another one on the side stream (streams.py: Net3D beside PNA) and autograd has made
-            # that stream current for this node: hand the whole backward pass to a helper thread and return, so that
-            # autograd's worker goes on with the other model's backward.  The two Python threads take turns at C-call
-            # granularity (every kernel launch releases the GIL); kernels, streams and their order are as before.  A
-            # callback at the end of the backward pass joins the helper and orders the caller's stream after it.
-            job = _Job(torch.cuda.current_stream(grad.device), ctx, grad.contiguous())
-            _helper().put(job)
-            torch.autograd.Variable._execution_engine.queue_callback(job.join)
-            return (None,) * (2 + len(ctx.params))
-        out = _model_backward(ctx, grad.contiguous(), direct)
+        out = _model_backward(ctx, grad, direct)
         if direct:
             # `.grad` is empty and nothing hooks the parameters: store the gradients here instead of sending them
             # through ~110 AccumulateGrad nodes (each a task of the autograd engine; and a gradient that is a view of
@@ -277,65 +257,6 @@ def _model_backward(ctx, grad, direct=False):
     return out
 
 
-# I3D_ASYNC_SIDE_BACKWARD=1: the side-stream model's backward pass is enqueued by a helper thread while autograd's worker
-# goes on with the other model.  EXPERIMENTAL, off: measured on MI355X (tools/step_segments.py, tools/ab.sh) the two
-# Python threads hand the GIL back and forth at every kernel launch and the backward segment gets SLOWER (1.85-2.0 ms
-# against 1.46-1.6 ms); it needs the enqueue loop itself out of Python (a native whole-model composite) to pay off.
-ASYNC_SIDE_BACKWARD = False
-
-
-class _Job:
-    """one model backward pass for the helper thread"""
-
-    def __init__(self, stream, ctx, grad):
-        self.stream, self.ctx, self.grad = stream, ctx, grad
-        self.done = threading.Event()
-        self.error = None
-        self.event = None
-
-    def run(self):
-        try:
-            with torch.no_grad(), torch.cuda.stream(self.stream):      # grad mode and current stream are per thread
-                out = _model_backward(self.ctx, self.grad, True)
-                for p, g in zip(self.ctx.params, out):
-                    if g is not None:
-                        p.grad = g
-                self.event = torch.cuda.Event()
-                self.event.record(self.stream)
-        except BaseException as e:      # re-raised in the thread that called backward()
-            self.error = e
-        finally:
-            self.ctx = self.grad = None
-            self.done.set()
-
-    def join(self):
-        """end-of-backward callback (runs with the caller's streams current)"""
-        self.done.wait()
-        if self.error is not None:
-            raise self.error
-        torch.cuda.current_stream(self.stream.device).wait_event(self.event)
-
-
-_helper_queue = None
-_helper_lock = threading.Lock()
-
-
-def _helper():
-    global _helper_queue
-    if _helper_queue is None:
-        with _helper_lock:
-            if _helper_queue is None:
-                import queue
-                q = queue.SimpleQueue()
-
-                def loop():
-                    while True:
-                        q.get().run()
-                threading.Thread(target=loop, name='i3d-side-backward', daemon=True).start()
-                _helper_queue = q
-    return _helper_queue
-
-
 # I3D_DIRECT_PARAM_GRADS=0: hand the parameter gradients to autograd's AccumulateGrad nodes instead
 DIRECT_PARAM_GRADS = os.environ.get('I3D_DIRECT_PARAM_GRADS', '1') != '0'
 
@@ -354,10 +275,6 @@ def register_grad_sink(module, fn, views=None):
     the weight-gradient kernels then write into them directly (_GradPool)."""
     st = model_state(module)
     st.sink, st.sink_views, st.pool = fn, views, None
-
-
-# I3D_FUSED_MODEL=0: one autograd node per block (or per PNA layer) instead of one per model
-FUSED_MODEL = True
 
 
 def _param_list(module):
@@ -398,7 +315,7 @@ def _param_list(module):
 def run_model(module, run):
     """module-level entry: `run()` is the plain forward of `module`.  Falls back to per-block autograd nodes when
     gradients are off, a tape is already recording, or nothing is trainable."""
-    if not FUSED_MODEL or not torch.is_grad_enabled() or getattr(_tls, 'tape', None) is not None:
+    if not torch.is_grad_enabled() or getattr(_tls, 'tape', None) is not None:
         return run()
     cached = _param_list(module)
     params = [p for p in cached if p.requires_grad]

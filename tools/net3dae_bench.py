@@ -91,12 +91,12 @@ class Case:
     def trunk(self, g):
         """latent vector and node state as autograd tensors: the model run per block (no whole-model node), head not called"""
         tape = importlib.import_module('3dinfomax_amd.tape')
-        prev, tape.FUSED_MODEL = tape.FUSED_MODEL, False
+        prev, tape.run_model = tape.run_model, lambda module, run: run()
         self.model.__dict__['_pair_head'] = lambda h, pidx: h          # shadows the method for this call
         try:
             latent, h = self.model(g, self.pidx)
         finally:
-            tape.FUSED_MODEL = prev
+            tape.run_model = prev
             del self.model.__dict__['_pair_head']
         return latent, h
 
