@@ -28,7 +28,7 @@ def __getattr__(name):
         from . import net3d_ae
         return net3d_ae.Net3DAE
     if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
-                'KLDivergenceMultiplePositives'):
+                'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -45,13 +45,17 @@ def __getattr__(name):
                 'contrastive_metrics'):
         from . import metrics
         return getattr(metrics, name)
+    if name in ('PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss', 'QM9DenormalizedL1', 'QM9DenormalizedL2',
+                'QM9SingleTargetDenormalizedL1'):
+        from . import task_metrics
+        return getattr(task_metrics, name)
     if name == 'Adam':
         from . import optim
         return optim.Adam
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -64,4 +68,6 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate', 'Uniformity', 'Alignment',
            'BatchVariance', 'DimensionCovariance', 'DistancePredictor', 'pairwise_distance_collate',
            'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate', 'NTXentMultiplePositivesSeparate2D',
-           'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance']
+           'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance',
+           'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
+           'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1']

@@ -350,6 +350,11 @@ _SIGNATURES = {
     'i3d_mmd_pair_bwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, c_double] + [_P] * 5),
     'i3d_kl_mp_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P]),
     'i3d_kl_mp_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
+    'i3d_masked_loss_partial_floats': (c_long, [c_int, c_int]),
+    'i3d_masked_loss_fwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'i3d_masked_loss_bwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    'i3d_task_moments_partial_floats': (c_long, [c_int, c_int]),
+    'i3d_task_moments': (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -552,3 +552,72 @@ class KLDivergenceMultiplePositives(_Separate2DBase):
             a, b = _RowNormalizeFn.apply(a), _RowNormalizeFn.apply(b)
         loss = _KLMultiplePositivesFn.apply(a.reshape(B, 2 * D), b, B, C, global_batch)
         return self._regularisers(loss, a.view(B, 2, D), b.view(B, C, D))
+
+
+# ---- fine-tuning on multi-task datasets with missing labels (csrc/task.hip) ---------------------------------------------------------------
+def _masked_loss_shapes(name, pred, target):
+    """[B, T] views of pred and target (1-D: [B, 1]); everything else is refused before any device work"""
+    if not (torch.is_tensor(pred) and torch.is_tensor(target)) or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f'{name}: pred and target of the same shape expected, got '
+                         f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred).__name__} and '
+                         f'{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}')
+    if pred.dim() not in (1, 2) or pred.numel() == 0:
+        raise ValueError(f'{name}: [batch, tasks] (or [batch]) with at least one element expected, got {tuple(pred.shape)}')
+    if pred.is_cuda != target.is_cuda:
+        raise ValueError(f'{name}: pred is on {pred.device}, target on {target.device}')
+    if pred.is_cuda and (pred.dtype != torch.float32 or target.dtype != torch.float32):
+        raise NotImplementedError(f'{name}: fp32 only on the device, got {pred.dtype} and {target.dtype}')
+    if pred.dim() == 1:
+        return pred.reshape(-1, 1), target.reshape(-1, 1)
+    return pred, target
+
+
+def _masked_loss_host(pred, target, kind):
+    """the same formula as a torch expression (CPU tensors: the host-logic tests).  torch.where on both sides of the product: a NaN or
+    inf prediction at an unlabelled position reaches neither the value nor the gradient"""
+    labelled = ~torch.isnan(target)
+    x, t = torch.where(labelled, pred, torch.zeros_like(pred)), torch.where(labelled, target, torch.zeros_like(target))
+    if kind == 0:
+        # max(x, 0) - x t + log1p(exp(-|x|)) with the gradient sigmoid(x) - t (also at x = 0, where clamp and abs have kinks)
+        term = torch.nn.functional.binary_cross_entropy_with_logits(x, t, reduction='none')
+    else:
+        term = (x - t) ** 2
+    return torch.where(labelled, term, torch.zeros_like(term)).sum() / labelled.sum()
+
+
+class _MaskedLossFn(torch.autograd.Function):
+    """mean over the labelled elements; the count stays on the device between the two passes (no host synchronisation)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind):
+        pred, target = pred.contiguous(), target.contiguous()
+        out = ops.masked_loss_fwd(pred, target, kind)
+        ctx.kind = kind
+        ctx.save_for_backward(pred, target, out)
+        return out.view(torch.float32)[4]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pred, target, out = ctx.saved_tensors
+        return ops.masked_loss_bwd(pred, target, ctx.kind, out, grad_out.contiguous().float().reshape(1)), None, None
+
+
+class _OGBNanLabelLoss(_Loss):
+    _kind = None
+
+    def forward(self, pred, target, **kwargs) -> Tensor:
+        p, t = _masked_loss_shapes(type(self).__name__, pred, target)
+        if p.is_cuda:
+            return _MaskedLossFn.apply(p, t.detach(), self._kind)
+        return _masked_loss_host(p, t.detach(), self._kind)
+
+
+class OGBNanLabelBCEWithLogitsLoss(_OGBNanLabelLoss):
+    """reference commons/losses.py:13-21: BCEWithLogitsLoss (mean) over the elements whose target is not NaN - the multi-task
+    MoleculeNet / OGB datasets.  No labelled element at all: NaN, the reference's mean over an empty selection, and a zero gradient."""
+    _kind = ops.MASKED_LOSS_KINDS['bce_with_logits']
+
+
+class OGBNanLabelMSELoss(_OGBNanLabelLoss):
+    """reference commons/losses.py:23-31: MSELoss (mean) over the elements whose target is not NaN."""
+    _kind = ops.MASKED_LOSS_KINDS['mse']

@@ -1056,3 +1056,44 @@ def kl_mp_bwd(z1, z2, batch, conf, inv_global_batch, grad_scale_dev):
     check(_lib.load().i3d_kl_mp_bwd(_p(z1), _p(z2), batch, conf, z2.shape[1], float(inv_global_batch), _p(grad_scale_dev), _p(dz1),
                                     _p(dz2), _stream()), 'i3d_kl_mp_bwd')
     return dz1, dz2
+
+
+# ---- fine-tuning: NaN-label losses and task moments (csrc/task.hip) -----------------------------------------------------------------------
+MASKED_LOSS_KINDS = {'bce_with_logits': 0, 'mse': 1}
+
+
+def masked_loss_fwd(pred, target, kind):
+    """pred, target [B, T] -> out [3] fp64: the mean over the elements whose target is not NaN, their count, and (first four bytes of
+    out[2]) the mean in fp32 - out.view(torch.float32)[4] is the loss tensor"""
+    _chk(pred)
+    _chk(target)
+    L = _lib.load()
+    B, T = pred.shape
+    partials = torch.empty(L.i3d_masked_loss_partial_floats(B, T) // 2, dtype=torch.float64, device=pred.device)
+    out = torch.empty(3, dtype=torch.float64, device=pred.device)
+    check(L.i3d_masked_loss_fwd(_p(pred), _p(target), B, T, int(kind), _p(partials), _p(out), _stream()), 'i3d_masked_loss_fwd')
+    return out
+
+
+def masked_loss_bwd(pred, target, kind, out, grad_out_dev):
+    """-> grad_pred [B, T]; the upstream scalar gradient grad_out_dev[0] and the labelled count out[1] are read on the device"""
+    _chk(pred)
+    _chk(target)
+    _chk(grad_out_dev)
+    B, T = pred.shape
+    grad = torch.empty_like(pred)
+    check(_lib.load().i3d_masked_loss_bwd(_p(pred), _p(target), B, T, int(kind), _p(out), _p(grad_out_dev), _p(grad), _stream()),
+          'i3d_masked_loss_bwd')
+    return grad
+
+
+def task_moments(pred, target):
+    """pred, target [B, T] -> table [T + 1, 10] fp64 on the device (include/infomax3d_hip.h: i3d_task_moments)"""
+    _chk(pred)
+    _chk(target)
+    L = _lib.load()
+    B, T = pred.shape
+    partials = torch.empty(L.i3d_task_moments_partial_floats(B, T) // 2, dtype=torch.float64, device=pred.device)
+    table = torch.empty(T + 1, 10, dtype=torch.float64, device=pred.device)
+    check(L.i3d_task_moments(_p(pred), _p(target), B, T, _p(partials), _p(table), _stream()), 'i3d_task_moments')
+    return table

@@ -1218,6 +1218,32 @@ int i3d_kl_mp_fwd(const float* z1, const float* z2, int batch, int conf, int dim
 int i3d_kl_mp_bwd(const float* z1, const float* z2, int batch, int conf, int dim, double inv_global_batch, const float* grad_scale,
                   float* dz1, float* dz2, void* stream);
 
+/* ---- fine-tuning: NaN-label losses and one-pass task moments (csrc/task.hip) ----
+ * pred, target [rows, tasks] row major (fp32), rows >= 1, tasks >= 1; anything else returns I3D_ERR_INVALID before a launch.
+ * i3d_masked_loss_fwd: stands for `self.bce_loss(pred[is_labeled], target[is_labeled])` / `self.mse_loss(...)` of reference
+ *   commons/losses.py:17-21, 27-31 (OGBNanLabelBCEWithLogitsLoss, OGBNanLabelMSELoss).  kind 0: BCE with logits in torch's stable form
+ *   max(x, 0) - x t + log1p(exp(-|x|)); kind 1: (x - t)^2.  An element is labelled iff its target is not NaN; pred at an unlabelled
+ *   position never reaches the result.  out (3 doubles): out[0] = the mean over the labelled elements (NaN when there is none),
+ *   out[1] = their count, the first four bytes of out[2] = out[0] rounded to fp32 (the loss tensor).  partials:
+ *   i3d_masked_loss_partial_floats(rows, tasks) floats, 8-byte aligned.  Terms and sums in fp64, fixed order, no atomics.
+ * i3d_masked_loss_bwd: the backward of the same call sites (the reference's index-put): grad_pred = grad_out[0] (sigmoid(x) - t) /
+ *   count (kind 0) or grad_out[0] 2 (x - t) / count (kind 1) where labelled, exactly 0.0f elsewhere; count = out[1] of the forward
+ *   and grad_out (null: 1) are read on the device.
+ * i3d_task_moments: stands for the per-metric reductions of reference trainer/metrics.py:23-32 (PearsonR), :48-54, :66-70, :98-101
+ *   (QM9SingleTargetDenormalizedL1, QM9DenormalizedL1, QM9DenormalizedL2), :77-79 (MAE), :142-145 (Rsquared) and :157-158
+ *   (MeanPredictorLoss), which Trainer.evaluate_metrics (trainer/trainer.py:174-183) runs one after the other.  table [tasks + 1][10]
+ *   (fp64), per task c: { n, sum p, sum t, sum (p - pbar_c)^2, sum (t - tbar_c)^2, sum (p - pbar_c)(t - tbar_c), sum |p - t|,
+ *   sum (p - t)^2, sum |t - tbar|, sum (t - tbar)^2 }, pbar_c / tbar_c the column means, tbar the mean of all targets; row `tasks`
+ *   holds the column totals.  Two passes (means first), four launches, no masking: NaN propagates as in the reference.  partials:
+ *   i3d_task_moments_partial_floats(rows, tasks) floats, 8-byte aligned. */
+long i3d_masked_loss_partial_floats(int rows, int tasks);
+int i3d_masked_loss_fwd(const float* pred, const float* target, int rows, int tasks, int kind, float* partials, double* out,
+                        void* stream);
+int i3d_masked_loss_bwd(const float* pred, const float* target, int rows, int tasks, int kind, const double* out,
+                        const float* grad_out, float* grad_pred, void* stream);
+long i3d_task_moments_partial_floats(int rows, int tasks);
+int i3d_task_moments(const float* pred, const float* target, int rows, int tasks, float* partials, double* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
