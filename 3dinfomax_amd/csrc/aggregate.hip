@@ -666,6 +666,8 @@ extern "C" int i3d_pna_aggregate_bwd_ex(const float* grad_out, const void* e_, i
                                         float* grad_e, void* stream) {
     const float* e = (const float*)e_;
     I3D_CHECK_ARG(!e_bf16 || (feat % 4 == 0 && (((uintptr_t)e_) & 7) == 0), "bf16 messages need feat % 4 == 0 and 8-byte alignment");
+    // (as the forward: the pair is only usable together, and the V = 4 kernel loads aff in 16-byte items)
+    I3D_CHECK_ARG(aff == nullptr || (feat % 4 == 0 && (((uintptr_t)aff) & 15) == 0), "aff needs feat % 4 == 0 and 16-byte alignment");
     I3D_CHECK_ARG(num_nodes >= 0 && feat > 0, "num_nodes >= 0 and feat > 0 required");
     AggCfg cfg;
     I3D_CHECK_ARG(make_cfg(aggregators, n_aggregators, scalers, n_scalers, force_scalers, avg_d_log, cfg) == 0,

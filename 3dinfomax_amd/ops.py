@@ -744,6 +744,17 @@ def pna_aggregate_bwd_aff(grad_out, e, aff, in_ptr, num_nodes, aggregators, scal
     return ge
 
 
+def pna_messages_normalized(e, aff):
+    """test entry (i3d_pna_messages_normalized_ex): the messages exactly as the aggregation kernels see them, fp32 [E, F] -
+    (e - mean) * scale + shift of a fp32 or bf16 e, aff [3, F] or None"""
+    bf16 = e.dtype == torch.bfloat16
+    _chk(e, torch.bfloat16 if bf16 else torch.float32)
+    out = torch.empty(e.shape, dtype=torch.float32, device=e.device)
+    check(_lib.load().i3d_pna_messages_normalized_ex(e.data_ptr(), int(bf16), _p(aff), e.shape[0], e.shape[1], _p(out), _stream()),
+          'i3d_pna_messages_normalized_ex')
+    return out
+
+
 WGRAD_PLAIN, WGRAD_BN, WGRAD_COMBINE = 0, 1, 2
 
 

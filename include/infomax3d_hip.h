@@ -632,7 +632,9 @@ long i3d_wgrad_multi_min_workspace_bytes(const I3dWgradProblem* problems, int n_
 int i3d_wgrad_multi(const I3dWgradProblem* problems, int n_problems, const I3dWgradOutput* outputs, int n_outputs,
                     void* workspace, long workspace_bytes, void* stream);
 
-/* i3d_pna_aggregate_fwd / _bwd with the messages read as (e - mean) * scale + shift (aff [3 feat], may be NULL) */
+/* i3d_pna_aggregate_fwd / _bwd with the messages read as (e - mean) * scale + shift (aff [3 feat], may be NULL).  A non-NULL aff
+ * needs feat % 4 == 0 and a 16-byte aligned aff (the kernels load it in 16-byte items): BOTH directions, and their _ex forms,
+ * return I3D_ERR_INVALID otherwise, before any launch.  The gradient is the one with respect to the normalised message. */
 int i3d_pna_aggregate_fwd_aff(const float* e, const float* aff, const int* in_ptr, int num_nodes, int feat,
                               const int* aggregators, int n_aggregators, const int* scalers, int n_scalers,
                               int force_scalers, float avg_d_log, float* out, void* stream);
