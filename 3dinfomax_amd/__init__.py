@@ -34,6 +34,9 @@ def __getattr__(name):
     if name == 'DistancePredictor':
         from . import distance_predictor
         return distance_predictor.DistancePredictor
+    if name in ('OGBGNN', 'GNN_node', 'GNN_node_Virtualnode', 'GINConv'):
+        from . import gin
+        return getattr(gin, name)
     if name in ('FCLayer', 'MLP'):
         from . import layers
         return getattr(layers, name)
@@ -55,7 +58,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -70,4 +73,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NodeDropCollate', 'Net3DAE', 'NTXentAE', 'contrastive_vae_collate', 'NTXentMultiplePositivesSeparate2D',
            'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance',
            'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
-           'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1']
+           'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
+           'GNN_node_Virtualnode', 'GINConv']

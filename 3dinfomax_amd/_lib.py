@@ -355,6 +355,10 @@ _SIGNATURES = {
     'i3d_masked_loss_bwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     'i3d_task_moments_partial_floats': (c_long, [c_int, c_int]),
     'i3d_task_moments': (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
+    'i3d_gin_chunk_edges': (c_int, []),
+    'i3d_gin_conv_bwd_partial_floats': (c_long, [c_int, c_int, c_int, c_int]),
+    'i3d_gin_conv_fwd': (c_int, [_P, _P, _P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'i3d_gin_conv_bwd': (c_int, [_P] * 3 + [c_int] + [_P] * 8 + [c_int, c_int, c_int] + [_P] * 5),
 }
 
 _lib = None

@@ -1108,3 +1108,52 @@ def task_moments(pred, target):
     table = torch.empty(T + 1, 10, dtype=torch.float64, device=pred.device)
     check(L.i3d_task_moments(_p(pred), _p(target), B, T, _p(partials), _p(table), _stream()), 'i3d_task_moments')
     return table
+
+
+# ---- GIN message step (csrc/gin.hip) -------------------------------------------------------------------------
+def code_sorted_index(codes, num_codes):
+    """(order [E], code_ptr [V + 1]) int32: the edge positions sorted by code (stable) and where every code's run starts in that
+    list - what i3d_gin_conv_bwd reduces the table gradient over.  Built once per batch, beside edge_codes; index plumbing in
+    torch (a stable sort and a count), on whatever device `codes` lives on."""
+    c = codes.long()
+    order = torch.sort(c, stable=True)[1].to(torch.int32)
+    ptr = torch.zeros(num_codes + 1, dtype=torch.int64, device=codes.device)
+    if c.numel():
+        torch.cumsum(torch.bincount(c, minlength=num_codes)[:num_codes], 0, out=ptr[1:])
+    return order, ptr.to(torch.int32)
+
+
+def gin_conv_fwd(h, vn, graph_ptr, num_graphs, T, codes, in_ptr, src_s, eps):
+    """-> (x, z): x = h + vn[graph of the node] (x is h itself when vn is None), z = (1 + eps) x + sum over the in-edges of
+    relu(x[src] + T[code]).  One launch (include/infomax3d_hip.h: i3d_gin_conv_fwd)."""
+    _chk(h)
+    _chk(T)
+    _chk(eps)
+    N, H = h.shape
+    E = 0 if codes is None else codes.shape[0]
+    x = h
+    if vn is not None:
+        _chk(vn)
+        x = torch.empty_like(h)
+    z = torch.empty_like(h)
+    check(_lib.load().i3d_gin_conv_fwd(_p(h), _p(vn), _p(graph_ptr), num_graphs, _p(T), T.shape[0], _p(codes), _p(in_ptr), _p(src_s),
+                                       _p(eps), N, E, H, _p(x) if vn is not None else None, _p(z), _stream()), 'i3d_gin_conv_fwd')
+    return x, z
+
+
+def gin_conv_bwd(g, x, T, codes, src_s, dst_s, out_ptr, out_epos, code_order, code_ptr, eps, dT_out=None):
+    """-> (dx [N, H], dT [V, H], deps [1]) from g = dL/dz (include/infomax3d_hip.h: i3d_gin_conv_bwd)"""
+    _chk(g)
+    _chk(x)
+    _chk(T)
+    N, H = x.shape
+    V = T.shape[0]
+    E = 0 if codes is None else codes.shape[0]
+    L = _lib.load()
+    partials = torch.empty(max(L.i3d_gin_conv_bwd_partial_floats(N, E, H, V), 2), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    dT = torch.empty_like(T) if dT_out is None else dT_out
+    deps = torch.empty(1, dtype=torch.float32, device=x.device)
+    check(L.i3d_gin_conv_bwd(_p(g), _p(x), _p(T), V, _p(codes), _p(src_s), _p(dst_s), _p(out_ptr), _p(out_epos), _p(code_order),
+                             _p(code_ptr), _p(eps), N, E, H, _p(partials), _p(dx), _p(dT), _p(deps), _stream()), 'i3d_gin_conv_bwd')
+    return dx, dT, deps

@@ -1246,6 +1246,34 @@ int i3d_masked_loss_bwd(const float* pred, const float* target, int rows, int ta
 long i3d_task_moments_partial_floats(int rows, int tasks);
 int i3d_task_moments(const float* pred, const float* target, int rows, int tasks, float* partials, double* table, void* stream);
 
+/* ---- GIN message step of the OGBGNN baseline (reference models/gin.py; csrc/gin.hip) ----
+ * N = num_nodes >= 1, E = num_edges >= 0, H = feat >= 1, V = num_codes in 1..256; anything else returns I3D_ERR_INVALID before a
+ * launch.  Edge arrays are in destination-sorted order (graph.GraphIndex); T [V, H] is the table of the bond embeddings of all V
+ * feature combinations and codes [E] names every edge's row (i3d_edge_codes); eps is a device scalar.  Rows are read four floats
+ * at a time when H % 4 == 0 and the buffers are 16-byte aligned, else one at a time.  Fixed summation order, no atomics, no [E, H]
+ * buffer in either direction.
+ * i3d_gin_conv_fwd: stands for `h_list[layer] + virtualnode_embedding[batch_id]` (models/gin.py:276) and GINConv.forward up to the
+ *   MLP (models/gin.py:103-108: bond_encoder, copy_u, relu(m + edge_embedding), sum, (1 + eps) x + new_x).  vn [B, H] with
+ *   graph_ptr [B + 1]: x = h + vn[graph of the node] is written to x [N, H]; vn null: x is h and the x argument is not touched.
+ *   z[v] = (1 + eps) x[v] + sum over the in-edges e of v (in_ptr order) of relu(x[src(e)] + T[codes[e]]).  The source of an edge
+ *   lies in the molecule of its destination.  One launch.
+ * i3d_gin_conv_bwd: the backward of the same lines from g = dL/dz [N, H], x as the forward left it (h without a virtual node):
+ *   dx[u] = (1 + eps) g[u] + sum over the out-edges e of u (out_ptr / out_epos order) of g[dst(e)] [x[u] + T[codes[e]] > 0];
+ *   dT[c] = sum over the edges of code c of g[dst(e)] [x[src(e)] + T[c] > 0], a zero row for a code without edges;
+ *   deps[0] = sum_v <g[v], x[v]>.  dT and deps are summed in fp64 and rounded once.  code_order [E]: the edge positions sorted by
+ *   code (stable), code_ptr [V + 1]: where every code's run starts in it; dT is reduced over chunks of i3d_gin_chunk_edges()
+ *   positions of that list, then per code in chunk order.  partials: i3d_gin_conv_bwd_partial_floats(N, E, H, V) floats, 8-byte
+ *   aligned.  Three launches (two when E = 0). */
+int i3d_gin_chunk_edges(void);
+long i3d_gin_conv_bwd_partial_floats(int num_nodes, int num_edges, int feat, int num_codes);
+int i3d_gin_conv_fwd(const float* h, const float* vn, const int* graph_ptr, int num_graphs, const float* T, int num_codes,
+                     const int* codes, const int* in_ptr, const int* src_s, const float* eps, int num_nodes, int num_edges, int feat,
+                     float* x, float* z, void* stream);
+int i3d_gin_conv_bwd(const float* g, const float* x, const float* T, int num_codes, const int* codes, const int* src_s,
+                     const int* dst_s, const int* out_ptr, const int* out_epos, const int* code_order, const int* code_ptr,
+                     const float* eps, int num_nodes, int num_edges, int feat, float* partials, float* dx, float* dT, float* deps,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
