@@ -37,6 +37,9 @@ def __getattr__(name):
     if name in ('OGBGNN', 'GNN_node', 'GNN_node_Virtualnode', 'GINConv'):
         from . import gin
         return getattr(gin, name)
+    if name in ('EGNN', 'EGCLayer'):
+        from . import egnn
+        return getattr(egnn, name)
     if name in ('FCLayer', 'MLP'):
         from . import layers
         return getattr(layers, name)
@@ -58,7 +61,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -74,4 +77,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance',
            'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
            'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
-           'GNN_node_Virtualnode', 'GINConv']
+           'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer']

@@ -359,6 +359,9 @@ _SIGNATURES = {
     'i3d_gin_conv_bwd_partial_floats': (c_long, [c_int, c_int, c_int, c_int]),
     'i3d_gin_conv_fwd': (c_int, [_P, _P, _P, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'i3d_gin_conv_bwd': (c_int, [_P] * 3 + [c_int] + [_P] * 8 + [c_int, c_int, c_int] + [_P] * 5),
+    'i3d_gate_reduce_max_feat': (c_int, []),
+    'i3d_gate_reduce_fwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 3),
+    'i3d_gate_reduce_bwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 4),
 }
 
 _lib = None
@@ -397,6 +400,9 @@ def load():
     lib.i3d_set_matmul_precision(int(prec == 'bf16'))
     _lib = lib
     return lib
+
+
+NOT_TAKEN = 1      # I3D_NOT_TAKEN: a valid call outside what the entry point's kernels cover; nothing was launched
 
 
 def check(rc, name):

@@ -233,14 +233,17 @@ def bond_graph(mol) -> BatchedMolGraph:
                            edata={'feat': torch.from_numpy(mol.bond_feat)})
 
 
-def complete_graph(mol, coords=None) -> BatchedMolGraph:
-    """Complete 3D distance graph of one molecule (reference datasets/qm9_dataset.py:233-244)."""
+def complete_graph(mol, coords=None, coordinates=False) -> BatchedMolGraph:
+    """Complete 3D distance graph of one molecule (reference datasets/qm9_dataset.py:233-244).  coordinates=True: the atom
+    positions as well, ndata['x'] float32 [n, 3] (:240) - what EGNN and the distance column of PNA read."""
     from .synth import complete_graph_edges, pairwise_distances
     coords = mol.coords if coords is None else coords
     src, dst = complete_graph_edges(mol.n_atoms)
     d = pairwise_distances(coords, src, dst)
-    return BatchedMolGraph(torch.from_numpy(src), torch.from_numpy(dst), mol.n_atoms,
-                           ndata={'feat': torch.from_numpy(mol.atom_feat)},
+    ndata = {'feat': torch.from_numpy(mol.atom_feat)}
+    if coordinates:
+        ndata['x'] = torch.from_numpy(np.ascontiguousarray(coords, dtype=np.float32)).reshape(-1, 3)
+    return BatchedMolGraph(torch.from_numpy(src), torch.from_numpy(dst), mol.n_atoms, ndata=ndata,
                            edata={'d': torch.from_numpy(d)})
 
 

@@ -1157,3 +1157,48 @@ def gin_conv_bwd(g, x, T, codes, src_s, dst_s, out_ptr, out_epos, code_order, co
     check(L.i3d_gin_conv_bwd(_p(g), _p(x), _p(T), V, _p(codes), _p(src_s), _p(dst_s), _p(out_ptr), _p(out_epos), _p(code_order),
                              _p(code_ptr), _p(eps), N, E, H, _p(partials), _p(dx), _p(dT), _p(deps), _stream()), 'i3d_gin_conv_bwd')
     return dx, dT, deps
+
+
+# ---- EGNN: gate, in-edge reduction, residual add (csrc/egnn.hip) -----------------------------------------------------------------
+def gate_reduce_max_feat():
+    return _lib.load().i3d_gate_reduce_max_feat()
+
+
+def gate_reduce_fwd(m, ws, bs, in_ptr, h, mean=False):
+    """-> (u [N, H], w [E]) with u[v] = h[v] + sum (mean) over the in-edges j of v of m[j] sigmoid(<ws, m[j]> + bs), w the gates; one
+    launch.  None when the kernel does not take the shape (include/infomax3d_hip.h: I3D_NOT_TAKEN): the caller composes the step."""
+    _chk(m)
+    _chk(h)
+    _chk(ws)
+    _chk(bs)
+    _chk(in_ptr, torch.int32)
+    E, H = m.shape
+    N = h.shape[0]
+    assert h.shape[1] == H and ws.numel() == H and bs.numel() == 1 and in_ptr.shape[0] == N + 1
+    u = torch.empty_like(h)
+    w = torch.empty(E, dtype=torch.float32, device=m.device)
+    rc = _lib.load().i3d_gate_reduce_fwd(_p(m), _p(ws), _p(bs), _p(in_ptr), _p(h), N, E, H, int(mean), _p(u), _p(w), _stream())
+    if rc == _lib.NOT_TAKEN:
+        return None
+    check(rc, 'i3d_gate_reduce_fwd')
+    return u, w
+
+
+def gate_reduce_bwd(gu, m, w, ws, in_ptr, mean=False):
+    """-> (gm [E, H], gws [H], gbs [1]) from gu = dL/du; dL/dh is gu itself.  One launch and the two column sums over the per-node
+    partial rows.  None when the kernel does not take the shape."""
+    _chk(gu)
+    _chk(m)
+    _chk(w)
+    _chk(ws)
+    E, H = m.shape
+    N = gu.shape[0]
+    gm = torch.empty_like(m)
+    part_ws = torch.empty(N, H, dtype=torch.float32, device=m.device)
+    part_bs = torch.empty(N, 1, dtype=torch.float32, device=m.device)
+    rc = _lib.load().i3d_gate_reduce_bwd(_p(gu), _p(m), _p(w), _p(ws), _p(in_ptr), N, E, H, int(mean), _p(gm), _p(part_ws),
+                                         _p(part_bs), _stream())
+    if rc == _lib.NOT_TAKEN:
+        return None
+    check(rc, 'i3d_gate_reduce_bwd')
+    return gm, colsum(part_ws), colsum(part_bs)

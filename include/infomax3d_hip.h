@@ -11,7 +11,8 @@
  *  - `stream` is a hipStream_t (pass torch.cuda.current_stream().cuda_stream); all work is enqueued
  *    asynchronously on it, nothing synchronises the device, no hidden allocations except where a
  *    `workspace` pointer is taken explicitly.
- *  - return value: I3D_OK (0) or a negative I3D_ERR_*; i3d_last_error() returns a thread-local message.
+ *  - return value: I3D_OK (0) or a negative I3D_ERR_*; i3d_last_error() returns a thread-local message.  The entry points that
+ *    say so return I3D_NOT_TAKEN (1) for a valid call outside what their kernels cover: nothing was launched, nothing written.
  *  - edge-sized tensors are in DESTINATION-SORTED ("epos") order: the in-edges of node v are the
  *    contiguous rows [in_ptr[v], in_ptr[v+1]) (stable w.r.t. edge id = DGL's mailbox order).
  *  - thread safety: the error string is thread-local.  PROCESS-WIDE state exists and is set through explicit setters only:
@@ -31,6 +32,7 @@ extern "C" {
 #define I3D_OK 0
 #define I3D_ERR_INVALID (-1)
 #define I3D_ERR_LAUNCH (-2)
+#define I3D_NOT_TAKEN 1
 
 /* activations: reference models/base_layers.py:9-20 (get_activation) */
 #define I3D_ACT_NONE 0
@@ -1273,6 +1275,25 @@ int i3d_gin_conv_bwd(const float* g, const float* x, const float* T, int num_cod
                      const int* dst_s, const int* out_ptr, const int* out_epos, const int* code_order, const int* code_ptr,
                      const float* eps, int num_nodes, int num_edges, int feat, float* partials, float* dx, float* dT, float* deps,
                      void* stream);
+
+/* ---- EGNN: soft-edge gate, in-edge reduction and residual add in one launch per direction (reference models/egnn.py:124-137;
+ * csrc/egnn.hip) ----
+ * N = num_nodes >= 1, E = num_edges >= 0, H = feat >= 1; anything else returns I3D_ERR_INVALID before a launch.  m [E, H] is in
+ * destination-sorted order, ws [H] and bs [1] are soft_edge_network's weight and bias, in_ptr [N + 1].  The kernels cover
+ * H % 4 == 0, H <= i3d_gate_reduce_max_feat() (512) and 16-byte aligned m, ws, h, u, gu, gm, part_ws; every other valid call
+ * returns I3D_NOT_TAKEN and the caller composes the step from i3d_soft_edge_*, i3d_segment_sum / i3d_segment_bcast and i3d_add.
+ * One wave per destination, fixed summation order, no atomics, no [E, H] buffer besides m and its gradient.
+ * i3d_gate_reduce_fwd: w[j] = sigmoid(<ws, m[j]> + bs) [E];  u[v] = h[v] + sum over the in-edges j of v of m[j] w[j], the sum
+ *   divided by the in-degree when reduce_mean != 0 (DGL fn.mean); a node without in-edges gets u[v] = h[v].  One launch.
+ * i3d_gate_reduce_bwd: from gu = dL/du [N, H], m and the w of the forward: g = gu[dst(j)] (over the in-degree for the mean),
+ *   gg_j = <g, m[j]> w_j (1 - w_j), gm[j] = g w_j + gg_j ws [E, H];  part_ws [N, H] row v = sum over the in-edges of v of
+ *   gg_j m[j], part_bs [N] entry v = the sum of gg_j (zeros without in-edges): their column sums over the nodes (i3d_colsum) are
+ *   dL/dws and dL/dbs.  dL/dh = gu.  One launch. */
+int i3d_gate_reduce_max_feat(void);
+int i3d_gate_reduce_fwd(const float* m, const float* ws, const float* bs, const int* in_ptr, const float* h, int num_nodes,
+                        int num_edges, int feat, int reduce_mean, float* u, float* w, void* stream);
+int i3d_gate_reduce_bwd(const float* gu, const float* m, const float* w, const float* ws, const int* in_ptr, int num_nodes,
+                        int num_edges, int feat, int reduce_mean, float* gm, float* part_ws, float* part_bs, void* stream);
 
 #ifdef __cplusplus
 }
