@@ -28,7 +28,8 @@ def __getattr__(name):
         from . import net3d_ae
         return net3d_ae.Net3DAE
     if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
-                'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss'):
+                'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'NTXentLocalGlobal',
+                'NTXentGlobalLocal'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -40,6 +41,9 @@ def __getattr__(name):
     if name in ('EGNN', 'EGCLayer'):
         from . import egnn
         return getattr(egnn, name)
+    if name == 'PNALocal':
+        from . import pna_local
+        return pna_local.PNALocal
     if name in ('FCLayer', 'MLP'):
         from . import layers
         return getattr(layers, name)
@@ -61,7 +65,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -77,4 +81,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance',
            'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
            'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
-           'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer']
+           'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal']

@@ -362,6 +362,11 @@ _SIGNATURES = {
     'i3d_gate_reduce_max_feat': (c_int, []),
     'i3d_gate_reduce_fwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 3),
     'i3d_gate_reduce_bwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 4),
+    'i3d_lg_row_chunk': (c_int, []),
+    'i3d_lg_ntxent_scratch_floats': (c_long, [c_int, c_int]),
+    'i3d_lg_ntxent_work_floats': (c_long, [c_int, c_int, c_int]),
+    'i3d_lg_ntxent_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P]),
+    'i3d_lg_ntxent_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -621,3 +621,121 @@ class OGBNanLabelBCEWithLogitsLoss(_OGBNanLabelLoss):
 class OGBNanLabelMSELoss(_OGBNanLabelLoss):
     """reference commons/losses.py:23-31: MSELoss (mean) over the elements whose target is not NaN."""
     _kind = ops.MASKED_LOSS_KINDS['mse']
+
+
+# ---- every node's 2D embedding against the 3D embeddings of whole molecules (csrc/localglobal.hip) ------------------------------------------
+def _local_global_graph_ptr(name, zn, zg, nodes_per_graph):
+    """int32 [B + 1] segment pointer of the node rows on zn's device, from a device tensor (batch_num_nodes()), a CPU tensor or a list;
+    a device cumsum, no host synchronisation.  Everything that cannot be a batch of this loss is refused before any device work."""
+    if nodes_per_graph is None:
+        raise ValueError(f'{name}: nodes_per_graph is None - the loss needs the number of nodes of every graph '
+                         '(graph.batch_num_nodes())')
+    if not (torch.is_tensor(zn) and torch.is_tensor(zg)) or zn.dim() != 2 or zg.dim() != 2 or zn.shape[1] != zg.shape[1]:
+        raise ValueError(f'{name}: zn [nodes, dim] and zg [graphs, dim] of one width expected, got '
+                         f'{tuple(zn.shape) if torch.is_tensor(zn) else type(zn).__name__} and '
+                         f'{tuple(zg.shape) if torch.is_tensor(zg) else type(zg).__name__}')
+    N, B = zn.shape[0], zg.shape[0]
+    on_host = not (torch.is_tensor(nodes_per_graph) and nodes_per_graph.is_cuda)
+    if on_host:
+        nodes_per_graph = torch.as_tensor(nodes_per_graph)
+    if nodes_per_graph.dim() != 1 or nodes_per_graph.shape[0] != B:
+        raise ValueError(f'{name}: nodes_per_graph has {tuple(nodes_per_graph.shape)} entries, zg has {B} graph rows')
+    if B < 2:
+        raise ValueError(f'{name}: a batch of {B} graph(s) has no negatives')
+    if nodes_per_graph.dtype.is_floating_point or nodes_per_graph.dtype == torch.bool:
+        raise ValueError(f'{name}: nodes_per_graph must hold integers, got {nodes_per_graph.dtype}')
+    if on_host and (int(nodes_per_graph.sum()) != N or int(nodes_per_graph.min()) < 0):
+        raise ValueError(f'{name}: nodes_per_graph sums to {int(nodes_per_graph.sum())} (smallest entry '
+                         f'{int(nodes_per_graph.min())}), zn has {N} node rows')
+    if N < 1 or zn.shape[1] < 1:
+        raise ValueError(f'{name}: zn of shape {tuple(zn.shape)} holds nothing to contrast')
+    if zn.dtype != torch.float32 or zg.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {zn.dtype} and {zg.dtype}')
+    if not (zn.is_cuda and zg.is_cuda):
+        raise RuntimeError(f'{name}: zn is on {zn.device}, zg on {zg.device} - the loss runs on the HIP kernels, there is no CPU '
+                           'fallback')
+    graph_ptr = torch.zeros(B + 1, dtype=torch.int32, device=zn.device)
+    graph_ptr[1:] = torch.cumsum(nodes_per_graph.to(zn.device, non_blocking=True), dim=0)
+    return graph_ptr
+
+
+def _aligned16(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _LocalGlobalFn(torch.autograd.Function):
+    """mean_i -log(e_{i,g(i)} / sum_{j != g(i)} e_ij) over the node rows; one C call per direction.  The [N, B] similarity is kept for
+    the backward pass, the per-row log-sum of the negatives next to it."""
+
+    @staticmethod
+    def forward(ctx, zn, zg, graph_ptr, tau, eps, norm):
+        zn, zg = _aligned16(zn), _aligned16(zg)
+        N, D = zn.shape
+        B = zg.shape[0]
+        L = _lib.load()
+        scratch = torch.empty(L.i3d_lg_ntxent_scratch_floats(N, B), dtype=torch.float32, device=zn.device)
+        loss = torch.empty(1, dtype=torch.float32, device=zn.device)
+        _lib.check(L.i3d_lg_ntxent_fwd(zn.data_ptr(), zg.data_ptr(), graph_ptr.data_ptr(), N, B, D, float(tau), float(eps), int(norm),
+                                       scratch.data_ptr(), loss.data_ptr(), ops._stream()), 'i3d_lg_ntxent_fwd')
+        ctx.cfg = (float(tau), float(eps), int(norm))
+        ctx.save_for_backward(zn, zg, graph_ptr, scratch)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        tau, eps, norm = ctx.cfg
+        zn, zg, graph_ptr, scratch = ctx.saved_tensors
+        N, D = zn.shape
+        B = zg.shape[0]
+        L = _lib.load()
+        work = torch.empty(L.i3d_lg_ntxent_work_floats(N, B, D), dtype=torch.float32, device=zn.device)
+        dzn, dzg = torch.empty_like(zn), torch.empty_like(zg)
+        gs = grad_out.contiguous().float()          # multiplied in on the device: no host read-back
+        _lib.check(L.i3d_lg_ntxent_bwd(zn.data_ptr(), zg.data_ptr(), graph_ptr.data_ptr(), N, B, D, tau, eps, norm, scratch.data_ptr(),
+                                       gs.data_ptr(), work.data_ptr(), dzn.data_ptr(), dzg.data_ptr(), ops._stream()),
+                   'i3d_lg_ntxent_bwd')
+        return dzn, dzg, None, None, None, None
+
+
+class NTXentLocalGlobal(_Loss):
+    """reference commons/losses.py:1117-1161: `forward(zn, zg, nodes_per_graph)` with zn [N, dim] the node embeddings of the batch
+    (PNALocal), zg [B, dim] the embeddings of whole molecules (the 3D network) and nodes_per_graph the B node counts (a device tensor,
+    a CPU tensor or a list).  The positive of node i is its own molecule, the negatives are the other B - 1; epsilon 1e-10 (:1153).
+    Single process only: the data-parallel form would need the global node count."""
+    _eps = 1e-10       # reference :1153
+
+    def __init__(self, norm: bool = True, tau: float = 0.5) -> None:
+        super().__init__()
+        self.norm, self.tau = norm, tau
+        self.group = None
+
+    def attach_group(self, group):
+        self.group = group
+        return self
+
+    def forward(self, zn, zg, nodes_per_graph=None, **kwargs) -> Tensor:
+        name = type(self).__name__
+        if self.group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(self.group) > 1:
+                raise NotImplementedError(f'{name} on a process group of more than one rank: the loss is a mean over the nodes of the '
+                                          'global batch, which needs the global node count')
+        graph_ptr = _local_global_graph_ptr(name, zn, zg, nodes_per_graph)
+        return _LocalGlobalFn.apply(zn, zg, graph_ptr, float(self.tau), self._eps, bool(self.norm))
+
+
+class NTXentGlobalLocal(_Loss):
+    """reference commons/losses.py:1164-1185: NTXentLocalGlobal with the first two arguments swapped, `forward(zg, zn,
+    nodes_per_graph)` - what SelfSupervisedAlternatingTrainer calls."""
+
+    def __init__(self, **kwargs) -> None:
+        super().__init__()
+        self.ntxent_local_global = NTXentLocalGlobal(**kwargs)
+
+    def attach_group(self, group):
+        self.ntxent_local_global.attach_group(group)
+        return self
+
+    def forward(self, zg, zn, nodes_per_graph=None, **kwargs) -> Tensor:
+        return self.ntxent_local_global(zn, zg, nodes_per_graph)

@@ -1202,3 +1202,7 @@ def gate_reduce_bwd(gu, m, w, ws, in_ptr, mean=False):
         return None
     check(rc, 'i3d_gate_reduce_bwd')
     return gm, colsum(part_ws), colsum(part_bs)
+
+
+# ---- local-global NT-Xent (csrc/localglobal.hip; called from losses._LocalGlobalFn) ---------------------------------------------------
+LG_ROW_CHUNK = 256      # rows per first-stage workgroup of the column reduction of the backward pass (i3d_lg_row_chunk)

@@ -1295,6 +1295,33 @@ int i3d_gate_reduce_fwd(const float* m, const float* ws, const float* bs, const 
 int i3d_gate_reduce_bwd(const float* gu, const float* m, const float* w, const float* ws, const int* in_ptr, int num_nodes,
                         int num_edges, int feat, int reduce_mean, float* gm, float* part_ws, float* part_bs, void* stream);
 
+/* ---- local-global NT-Xent: every node embedding against the graph embeddings (reference commons/losses.py:1117-1185;
+ * csrc/localglobal.hip) ----
+ * zn [n, dim] node embeddings, zg [b, dim] graph embeddings, graph_ptr [b + 1] int32: the nodes of graph j are the rows
+ * graph_ptr[j] .. graph_ptr[j + 1] - 1 (a graph may be empty).  g(i) = the segment that holds row i (upper bound - 1, clamped to
+ * [0, b - 1]: no content of graph_ptr makes a kernel read or write out of bounds).
+ *   s'_ij = zn_i . zg_j / (|zn_i| |zg_j| + eps)   (norm == 0: the plain dot product, eps unused)
+ *   loss  = mean_i ( log sum_{j != g(i)} exp(s'_ij / tau)  -  s'_{i g(i)} / tau )
+ * The negatives are summed over the columns other than g(i) with their maximum taken out: finite wherever fp32 holds the result.
+ * n >= 1, b >= 2, dim >= 1, tau > 0 and non-null pointers, anything else returns I3D_ERR_INVALID before a launch.
+ * Deterministic: fixed summation orders that depend on (n, b, dim) only, no atomics.
+ * i3d_lg_ntxent_scratch_floats: floats of `scratch`, written by _fwd and read by _bwd (row norms, per-row log-sum, row losses,
+ *   the [n, b] similarity).  i3d_lg_ntxent_work_floats: floats of `work` of _bwd (dL/dsim [n, b], the per-chunk column partials
+ *   [ceil(n / i3d_lg_row_chunk()), b] and the slices of the K = n product).
+ * i3d_lg_ntxent_fwd: row norms, zn zg^T (i3d_gemm_f32), the row kernel, the sum of the n row losses in fp64 -> loss [1].
+ * i3d_lg_ntxent_bwd: dzn [n, dim], dzg [b, dim] of grad_scale_dev[0] * loss (grad_scale_dev: one device float, or null = 1):
+ *   dS'_ij = gs / (n tau) (j == g(i) ? -1 : e_ij / neg_i),  H = dS' / (a_i b_j + eps),  dzn = H zg + ca . zn,
+ *   dzg = H^T zn + cb . zg with ca_i = -(1 / a_i) sum_j H_ij s'_ij b_j, cb_j = -(1 / b_j) sum_i H_ij s'_ij a_i; a zero row
+ *   (a_i = 0 or b_j = 0) gets a zero norm term.  cb is reduced in two stages over row chunks of i3d_lg_row_chunk() rows. */
+int i3d_lg_row_chunk(void);
+long i3d_lg_ntxent_scratch_floats(int n, int b);
+long i3d_lg_ntxent_work_floats(int n, int b, int dim);
+int i3d_lg_ntxent_fwd(const float* zn, const float* zg, const int* graph_ptr, int n, int b, int dim, float tau, float eps,
+                      int norm, float* scratch, float* loss, void* stream);
+int i3d_lg_ntxent_bwd(const float* zn, const float* zg, const int* graph_ptr, int n, int b, int dim, float tau, float eps,
+                      int norm, const float* scratch, const float* grad_scale_dev, float* work, float* dzn, float* dzg,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
