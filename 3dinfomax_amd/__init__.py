@@ -29,7 +29,8 @@ def __getattr__(name):
         return net3d_ae.Net3DAE
     if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
                 'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'NTXentLocalGlobal',
-                'NTXentGlobalLocal'):
+                'NTXentGlobalLocal', 'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching',
+                'NTXentMaximumSimilarity'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -81,4 +82,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMMDSeparate2D', 'KLDivergenceMultiplePositives', 'Conformer3DVariance', 'Conformer2DVariance',
            'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
            'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
-           'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal']
+           'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal',
+           'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity']

@@ -367,6 +367,13 @@ _SIGNATURES = {
     'i3d_lg_ntxent_work_floats': (c_long, [c_int, c_int, c_int]),
     'i3d_lg_ntxent_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P]),
     'i3d_lg_ntxent_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P]),
+    'i3d_conf_match_max_conformers': (c_int, []),
+    'i3d_per_conf_max_conformers': (c_int, []),
+    'i3d_conf_match_work_floats': (c_long, [c_int]),
+    'i3d_conf_match_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float] + [_P] * 8),
+    'i3d_conf_match_bwd': (c_int, [_P] * 9 + [c_int, c_int, c_int, c_int, c_int, c_float] + [_P] * 5),
+    'i3d_per_conf_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
+    'i3d_per_conf_bwd': (c_int, [_P] * 5 + [c_int, c_int, c_int, c_float] + [_P] * 5),
 }
 
 _lib = None

@@ -480,6 +480,130 @@ class NTXentMMDSeparate2D(_Separate2DBase):
         return self._regularisers(loss, x.view(B, C, D), y.view(B, C, D))
 
 
+# ---- set matching and per-conformer terms (csrc/confmatch.hip) ------------------------------------------------------------------------
+class _ConfMatchFn(torch.autograd.Function):
+    """-mean_i log(pos_i / den_i) where every molecule pair enters through ONE entry of its C x C block of the [B C, B C] similarity: the
+    smallest (mode 0) or the largest (mode 1).  The backward pass gathers from those entries; the only [B C, B C] tensor is the
+    similarity itself."""
+
+    @staticmethod
+    def forward(ctx, z1v, z2, batch, conf, tau, norm, mode):
+        z1v, z2 = z1v.contiguous(), z2.contiguous()
+        if norm:
+            n1, n2 = ops.row_norms(z1v), ops.row_norms(z2)
+        else:
+            n1 = n2 = torch.ones(z1v.shape[0], dtype=torch.float32, device=z1v.device)
+        sim = ops.gemm(z1v, z2, trans_b=True)
+        sel, row_den, pos_j, pos_lu, loss = ops.conf_match_fwd(sim, n1, n2, batch, conf, mode, tau)
+        ctx.cfg = (batch, conf, tau, norm, mode)
+        ctx.save_for_backward(z1v, z2, n1, n2, sim, sel, row_den, pos_j, pos_lu)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, tau, norm, mode = ctx.cfg
+        z1v, z2, n1, n2, sim, sel, row_den, pos_j, pos_lu = ctx.saved_tensors
+        dz1, dz2 = ops.conf_match_bwd(sim, z1v, z2, n1, n2, sel, row_den, pos_j, pos_lu, batch, conf, mode, norm, tau,
+                                      grad_out.contiguous().float())
+        return dz1, dz2, None, None, None, None, None
+
+
+class _PerConformerFn(torch.autograd.Function):
+    """the V2 (mode 0) and V3 (mode 1) losses from the [B, B C] similarity of the 2D embeddings z1 and the 3D embeddings z2"""
+
+    @staticmethod
+    def forward(ctx, z1, z2, batch, conf, tau, norm, mode):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        if norm:
+            n1, n2 = ops.row_norms(z1), ops.row_norms(z2)
+        else:
+            n1 = torch.ones(z1.shape[0], dtype=torch.float32, device=z1.device)
+            n2 = torch.ones(z2.shape[0], dtype=torch.float32, device=z1.device)
+        sim = ops.gemm(z1, z2, trans_b=True)
+        den, pos, loss = ops.per_conf_fwd(sim, n1, n2, batch, conf, mode, tau)
+        ctx.cfg = (batch, conf, tau, norm, mode)
+        ctx.save_for_backward(z1, z2, n1, n2, sim, den, pos)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, tau, norm, mode = ctx.cfg
+        z1, z2, n1, n2, sim, den, pos = ctx.saved_tensors
+        dsim, ca, cb = ops.per_conf_bwd(sim, n1, n2, den, pos, batch, conf, mode, tau, grad_out.contiguous().float())
+        dz1 = ops.gemm(dsim, z2)
+        dz2 = ops.gemm(dsim, z1, trans_a=True)
+        if norm:
+            ops.row_axpy(z1, ca, dz1)
+            ops.row_axpy(z2, cb, dz2)
+        return dz1, dz2, None, None, None, None, None
+
+
+class _ConfMatchBase(_Separate2DBase):
+    _mode = None
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _separate2d_shapes(type(self).__name__, z1, z2)
+        self._refuse_unsupported()
+        loss = _ConfMatchFn.apply(z1.reshape(B * C, D), z2, B, C, float(self.tau), bool(self.norm), ops.CONF_MATCH_MODES[self._mode])
+        return self._regularisers(loss, z1.view(B, C, D), z2.view(B, C, D))
+
+
+class NTXentMinimumMatching(_ConfMatchBase):
+    """reference commons/losses.py:747-794: z1 [B, C D] holds one 2D embedding per conformer, z2 [B C, D] the 3D embeddings, molecule
+    major.  The similarity of two molecules is the SMALLEST entry of their C x C block; the positive of molecule i is the largest
+    matched entry s'[(i, l), (j, l)] over every column molecule j and every l - the reference's amax over the blocks' diagonals runs
+    over j as well.  No epsilon.  A tie goes to the lowest index (torch splits its gradient evenly)."""
+    _mode = 'min'
+
+
+class NTXentMaximumSimilarity(_ConfMatchBase):
+    """reference commons/losses.py:839-886: as NTXentMinimumMatching with the LARGEST entry of every C x C block; the positive of
+    molecule i is the largest entry of its own block."""
+    _mode = 'max'
+
+
+def _per_conformer_shapes(name, z1, z2):
+    """(B, C, D) of z1 [B, D] and z2 [B C, D]; everything else is refused before any device work"""
+    if z1.dim() != 2 or z2.dim() != 2:
+        raise ValueError(f'{name}: z1 [batch, dim] and z2 [batch * conformers, dim] expected, got {tuple(z1.shape)} and '
+                         f'{tuple(z2.shape)}')
+    B, D = z1.shape
+    if z2.shape[1] != D:
+        raise ValueError(f'{name}: z1 has {D} columns, z2 has {z2.shape[1]}')
+    if B < 1 or z2.shape[0] % B != 0:
+        raise ValueError(f'{name}: the {z2.shape[0]} rows of z2 are not a multiple of the batch size {B}')
+    C = z2.shape[0] // B
+    if C < 1 or C > ops.PER_CONF_MAX_CONFORMERS:
+        raise NotImplementedError(f'{name}: {C} conformers per molecule, the kernels are built for 1..{ops.PER_CONF_MAX_CONFORMERS}')
+    if B < 2:
+        raise ValueError(f'{name}: a batch of {B} has no negatives')
+    if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {z1.dtype} and {z2.dtype}')
+    return B, C, D
+
+
+class _PerConformerBase(_Separate2DBase):
+    _mode = None
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _per_conformer_shapes(type(self).__name__, z1, z2)
+        self._refuse_unsupported()
+        loss = _PerConformerFn.apply(z1, z2, B, C, float(self.tau), bool(self.norm), ops.PER_CONF_MODES[self._mode])
+        return self._regularisers(loss, z1, z2.view(B, C, D))
+
+
+class NTXentMultiplePositivesV2(_PerConformerBase):
+    """reference commons/losses.py:598-643: z1 [B, D], z2 [B C, D] molecule major.  pos_i = the sum over the molecule's C conformers,
+    den_i = the sum over conformer 0 of every OTHER molecule - the reference builds its negatives from z2[:, 0] only.  No epsilon."""
+    _mode = 'v2'
+
+
+class NTXentMultiplePositivesV3(_PerConformerBase):
+    """reference commons/losses.py:646-689: one NT-Xent term per (molecule, conformer): the positive is that conformer, the negatives
+    are the same conformer index of every other molecule; the mean runs over the B C terms.  No epsilon."""
+    _mode = 'v3'
+
+
 # ---- the conformers as one diagonal Gaussian per molecule (csrc/klmp.hip) --------------------------------------------------------------
 def _kl_shapes(name, z1, z2):
     """(B, C, D) of z1 [B, 2 D] (mean | log-variance) and z2 [B C, D]; everything else is refused before any device work"""

@@ -1046,6 +1046,65 @@ def mmd_pair_bwd(X, Y, cross, intra, bandwidth, sim, dsim, batch, conf, kernel_n
     return dX, dY
 
 
+# ---- set-matching and per-conformer NT-Xent (csrc/confmatch.hip) -------------------------------------------------------------------------
+PER_CONF_MAX_CONFORMERS = 64
+CONF_MATCH_MODES = {'min': 0, 'max': 1}
+PER_CONF_MODES = {'v2': 0, 'v3': 1}
+
+
+def conf_match_fwd(sim, n1, n2, batch, conf, mode, tau):
+    """sim [B C, B C] (rows: the conformer-wise 2D view, columns: the 3D view) -> (sel [B, B] uint8: l C + u of the selected entry of
+    every molecule pair, row_den [B] fp64, pos_j / pos_lu [B] int32: where the positive sits, loss [1])"""
+    _chk(sim)
+    dev = sim.device
+    sel = torch.empty(batch, batch, dtype=torch.uint8, device=dev)
+    dsel = torch.empty(batch, batch, dtype=torch.uint8, device=dev) if mode == CONF_MATCH_MODES['min'] else None
+    row_den = torch.empty(batch, dtype=torch.float64, device=dev)
+    row_pos = torch.empty(batch, dtype=torch.float64, device=dev)
+    pos_j = torch.empty(batch, dtype=torch.int32, device=dev)
+    pos_lu = torch.empty(batch, dtype=torch.int32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(_lib.load().i3d_conf_match_fwd(_p(sim), _p(n1), _p(n2), batch, conf, int(mode), float(tau), _p(sel), _p(dsel), _p(row_den),
+                                         _p(row_pos), _p(pos_j), _p(pos_lu), _p(loss), _stream()), 'i3d_conf_match_fwd')
+    return sel, row_den, pos_j, pos_lu, loss
+
+
+def conf_match_bwd(sim, z1v, z2, n1, n2, sel, row_den, pos_j, pos_lu, batch, conf, mode, norm, tau, grad_scale_dev):
+    """-> (dz1v, dz2) from one selected entry per molecule pair; the upstream scalar gradient grad_scale_dev[0] is multiplied in on the
+    device"""
+    _chk(z1v)
+    _chk(z2)
+    L = _lib.load()
+    work = torch.empty(L.i3d_conf_match_work_floats(batch), dtype=torch.float32, device=sim.device)
+    dz1, dz2 = torch.empty_like(z1v), torch.empty_like(z2)
+    check(L.i3d_conf_match_bwd(_p(sim), _p(z1v), _p(z2), _p(n1), _p(n2), _p(sel), _p(row_den), _p(pos_j), _p(pos_lu), batch, conf,
+                               z2.shape[1], int(mode), int(bool(norm)), float(tau), _p(grad_scale_dev), _p(work), _p(dz1), _p(dz2),
+                               _stream()), 'i3d_conf_match_bwd')
+    return dz1, dz2
+
+
+def per_conf_fwd(sim, n1, n2, batch, conf, mode, tau):
+    """sim [B, B C] -> (den, pos: [B] (V2) or [B C] (V3), fp64; loss [1])"""
+    _chk(sim)
+    terms = batch * conf if mode == PER_CONF_MODES['v3'] else batch
+    den = torch.empty(terms, dtype=torch.float64, device=sim.device)
+    pos = torch.empty(terms, dtype=torch.float64, device=sim.device)
+    loss = torch.empty(1, dtype=torch.float32, device=sim.device)
+    check(_lib.load().i3d_per_conf_fwd(_p(sim), _p(n1), _p(n2), batch, conf, int(mode), float(tau), _p(den), _p(pos), _p(loss),
+                                       _stream()), 'i3d_per_conf_fwd')
+    return den, pos, loss
+
+
+def per_conf_bwd(sim, n1, n2, den, pos, batch, conf, mode, tau, grad_scale_dev):
+    """-> (dsim [B, B C], ca [B], cb [B C]); the upstream scalar gradient grad_scale_dev[0] is multiplied in on the device"""
+    dsim = torch.empty_like(sim)
+    ca = torch.empty(batch, dtype=torch.float32, device=sim.device)
+    cb = torch.empty(batch * conf, dtype=torch.float32, device=sim.device)
+    check(_lib.load().i3d_per_conf_bwd(_p(sim), _p(n1), _p(n2), _p(den), _p(pos), batch, conf, int(mode), float(tau),
+                                       _p(grad_scale_dev), _p(dsim), _p(ca), _p(cb), _stream()), 'i3d_per_conf_bwd')
+    return dsim, ca, cb
+
+
 # ---- KLDivergenceMultiplePositives (csrc/klmp.hip) -------------------------------------------------------------------------------------
 def kl_mp_fwd(z1, z2, batch, conf, inv_global_batch, want_loss=True):
     """z1 [B, 2 D] (mean | log-variance), z2 [B C, D] -> (stats [B, 3] fp64: kl_b, sum_d var(z2_b), sum_d exp(s1_b); loss [1] =

@@ -1322,6 +1322,43 @@ int i3d_lg_ntxent_bwd(const float* zn, const float* zg, const int* graph_ptr, in
                       int norm, const float* scratch, const float* grad_scale_dev, float* work, float* dzn, float* dzg,
                       void* stream);
 
+/* ---- set-matching and per-conformer NT-Xent (reference commons/losses.py:598-689, 747-794, 839-886; csrc/confmatch.hip) ----
+ * B = batch >= 2 molecules, C = conf conformers, D = dim >= 1, tau > 0, s' = sim / (n1 n2) (n1, n2: the row norms, ones without
+ * normalisation), no epsilon.  Anything else returns I3D_ERR_INVALID before a launch.  Fixed summation orders, no atomics.
+ * Matching losses (C in 1..i3d_conf_match_max_conformers() = 8, N = B C <= 46340): sim [N, N] = z1v z2^T, rows (i, l), columns (j, u).
+ *   mode 0, NTXentMinimumMatching: den_i = sum_{j != i} exp(min_{l, u} s'[(i, l), (j, u)] / tau), pos_i = exp(max over EVERY j and l
+ *   of s'[(i, l), (j, l)] / tau) - the reference's amax over the matched diagonal runs over all column molecules.  mode 1,
+ *   NTXentMaximumSimilarity: den_i = sum_{j != i} exp(max_{l, u} s' / tau), pos_i = exp(max_{l, u} s'[(i, l), (i, u)] / tau).
+ *   loss[0] = -mean_i log(pos_i / den_i).  Ties: the lowest l, then the lowest u wins inside a molecule pair, the lowest j, then the
+ *   lowest l among the candidates of the positive (torch splits a tie's gradient evenly; a tie has measure zero).  A NaN wins every
+ *   selection.
+ * i3d_conf_match_fwd: sel [B, B] bytes = l C + u of the selected entry of every molecule pair; dsel [B, B] bytes (mode 0 only, may
+ *   be null in mode 1) = the l of the pair's largest matched entry; row_den, row_pos [B] (fp64); pos_j, pos_lu [B] (int32) = the
+ *   column molecule and l C + u of the positive's entry.
+ * i3d_conf_match_bwd: dz1 [N, D] (the gradient of z1v) and dz2 [N, D], times grad_scale[0] read on the device (null: 1), from one
+ *   selected entry per molecule pair and one positive per molecule: no [N, N] gradient, no matrix product.  norm == 0: the norm
+ *   terms are left out (n1 = n2 = ones).  work: i3d_conf_match_work_floats(B) floats.
+ * Per-conformer losses (C in 1..i3d_per_conf_max_conformers() = 64, B^2 C < 2^31): sim [B, N] = z1 z2^T, z2 molecule major.
+ *   mode 0, NTXentMultiplePositivesV2: pos_i = sum_u P[i, (i, u)], den_i = sum_{j != i} P[i, (j, 0)], den / pos [B].  mode 1,
+ *   NTXentMultiplePositivesV3: pos_iu = P[i, (i, u)], den_iu = sum_{j != i} P[i, (j, u)], den / pos [B C].  P = exp(s' / tau);
+ *   loss[0] = -mean log(pos / den) over the B (B C) terms.  The positives are left out of the sums, never subtracted.
+ * i3d_per_conf_bwd: dsim = dL/d sim [B, N] (exact zeros where an entry is in no sum) and the norm-path coefficients ca [B], cb [N]
+ *   (dz1 = dsim z2 + ca z1, dz2 = dsim^T z1 + cb z2), times grad_scale[0] read on the device (null: 1). */
+int i3d_conf_match_max_conformers(void);
+int i3d_per_conf_max_conformers(void);
+long i3d_conf_match_work_floats(int batch);
+int i3d_conf_match_fwd(const float* sim, const float* n1, const float* n2, int batch, int conf, int mode, float tau,
+                       unsigned char* sel, unsigned char* dsel, double* row_den, double* row_pos, int* pos_j, int* pos_lu,
+                       float* loss, void* stream);
+int i3d_conf_match_bwd(const float* sim, const float* z1v, const float* z2, const float* n1, const float* n2,
+                       const unsigned char* sel, const double* row_den, const int* pos_j, const int* pos_lu, int batch, int conf,
+                       int dim, int mode, int norm, float tau, const float* grad_scale, float* work, float* dz1, float* dz2,
+                       void* stream);
+int i3d_per_conf_fwd(const float* sim, const float* n1, const float* n2, int batch, int conf, int mode, float tau, double* den,
+                     double* pos, float* loss, void* stream);
+int i3d_per_conf_bwd(const float* sim, const float* n1, const float* n2, const double* den, const double* pos, int batch, int conf,
+                     int mode, float tau, const float* grad_scale, float* dsim, float* ca, float* cb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
