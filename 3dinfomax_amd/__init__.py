@@ -45,6 +45,9 @@ def __getattr__(name):
     if name == 'PNALocal':
         from . import pna_local
         return pna_local.PNALocal
+    if name in ('GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP'):
+        from . import geomol
+        return getattr(geomol, name)
     if name in ('FCLayer', 'MLP'):
         from . import layers
         return getattr(layers, name)
@@ -66,7 +69,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local', 'geomol'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -83,4 +86,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss',
            'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
            'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal',
-           'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity']
+           'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity',
+           'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP']

@@ -362,6 +362,10 @@ _SIGNATURES = {
     'i3d_gate_reduce_max_feat': (c_int, []),
     'i3d_gate_reduce_fwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 3),
     'i3d_gate_reduce_bwd': (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 4),
+    'i3d_geomol_edge_fwd': (c_int, [_P] * 4 + [c_int] * 3 + [_P] * 2),
+    'i3d_geomol_edge_bwd': (c_int, [_P] * 5 + [c_int] * 3 + [_P] * 3),
+    'i3d_geomol_residual_fwd': (c_int, [_P] * 3 + [c_long, c_int] + [_P] * 2),
+    'i3d_geomol_residual_bwd': (c_int, [_P] * 3 + [c_long, c_int] + [_P] * 4),
     'i3d_lg_row_chunk': (c_int, []),
     'i3d_lg_ntxent_scratch_floats': (c_long, [c_int, c_int]),
     'i3d_lg_ntxent_work_floats': (c_long, [c_int, c_int, c_int]),

@@ -1263,5 +1263,63 @@ def gate_reduce_bwd(gu, m, w, ws, in_ptr, mean=False):
     return gm, colsum(part_ws), colsum(part_bs)
 
 
+# ---- GeoMol's message-passing step (csrc/geomol.hip) -----------------------------------------------------------------------------
+GEOMOL_PARTIAL_FLOATS = 2048      # I3D_GEOMOL_PARTIAL_FLOATS (include/infomax3d_hip.h)
+
+
+def geomol_edge_fwd(F, PQ, src_s, dst_s):
+    """h [E, H] = relu(F + P[src] + Q[dst]); PQ [N, 2H] holds P | Q.  One launch."""
+    _chk(F)
+    _chk(PQ)
+    E, H = F.shape
+    N = PQ.shape[0]
+    assert PQ.shape[1] == 2 * H and src_s.shape[0] == E and dst_s.shape[0] == E
+    h = torch.empty_like(F)
+    check(_lib.load().i3d_geomol_edge_fwd(_p(F), _p(PQ), _p(src_s), _p(dst_s), N, E, H, _p(h), _stream()), 'i3d_geomol_edge_fwd')
+    return h
+
+
+def geomol_edge_bwd(g, h, in_ptr, out_ptr, out_epos):
+    """-> (dF [E, H], dPQ [N, 2H] = dP | dQ) from g = dL/dh and the forward's h.  One launch."""
+    _chk(g)
+    _chk(h)
+    _chk(in_ptr, torch.int32)
+    _chk(out_ptr, torch.int32)
+    E, H = h.shape
+    N = in_ptr.shape[0] - 1
+    assert g.shape == h.shape and out_ptr.shape[0] == N + 1 and out_epos.shape[0] == E
+    dF = torch.empty_like(h)
+    dPQ = torch.empty(N, 2 * H, dtype=torch.float32, device=h.device)
+    check(_lib.load().i3d_geomol_edge_bwd(_p(g), _p(h), _p(in_ptr), _p(out_ptr), _p(out_epos), N, E, H, _p(dF), _p(dPQ), _stream()),
+          'i3d_geomol_edge_bwd')
+    return dF, dPQ
+
+
+def geomol_residual_fwd(a, b, eps):
+    """(1 + eps) a + b on [R, H]; eps a device tensor [1]: no host synchronisation"""
+    _chk(a)
+    _chk(b)
+    _chk(eps)
+    assert a.shape == b.shape and eps.numel() == 1
+    out = torch.empty_like(a)
+    check(_lib.load().i3d_geomol_residual_fwd(_p(a), _p(b), _p(eps), a.shape[0], a.shape[1], _p(out), _stream()),
+          'i3d_geomol_residual_fwd')
+    return out
+
+
+def geomol_residual_bwd(g, a, eps):
+    """-> (da = (1 + eps) g, deps [1] = <g, a>, fp64 accumulation rounded once).  dL/db is g itself."""
+    _chk(g)
+    _chk(a)
+    _chk(eps)
+    assert g.shape == a.shape and eps.numel() == 1
+    da = torch.empty_like(g)
+    deps = torch.empty(1, dtype=torch.float32, device=g.device)
+    partials = torch.empty(GEOMOL_PARTIAL_FLOATS, dtype=torch.float32, device=g.device)
+    check(_lib.load().i3d_geomol_residual_bwd(_p(g), _p(a), _p(eps), a.shape[0], a.shape[1], _p(partials), _p(da), _p(deps),
+                                              _stream()), 'i3d_geomol_residual_bwd')
+    return da, deps
+
+
 # ---- local-global NT-Xent (csrc/localglobal.hip; called from losses._LocalGlobalFn) ---------------------------------------------------
 LG_ROW_CHUNK = 256      # rows per first-stage workgroup of the column reduction of the backward pass (i3d_lg_row_chunk)

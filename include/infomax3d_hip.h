@@ -1295,6 +1295,30 @@ int i3d_gate_reduce_fwd(const float* m, const float* ws, const float* bs, const 
 int i3d_gate_reduce_bwd(const float* gu, const float* m, const float* w, const float* ws, const int* in_ptr, int num_nodes,
                         int num_edges, int feat, int reduce_mean, float* gm, float* part_ws, float* part_bs, void* stream);
 
+/* ---- GeoMol's message-passing step (reference models/geomol_mpnn.py:72-74, :93-99; csrc/geomol.hip) ----
+ * N = num_nodes >= 1, E = num_edges >= 0, H = feat >= 1, rows >= 0; anything else returns I3D_ERR_INVALID before a launch.  Edge
+ * arrays and edge rows are in destination-sorted order (graph.GraphIndex).  fp32; rows are read four floats at a time when the width
+ * allows and the buffers are 16-byte aligned, else one at a time: any H is taken.  Fixed summation order, no atomics, no buffer
+ * beyond the caller's.
+ * i3d_geomol_edge_fwd: h[j] = relu((F[j] + P[src_s[j]]) + Q[dst_s[j]]), F [E, H] (the bias of the edge Linear already in it),
+ *   PQ [N, 2H]: row v = P[v] | Q[v], the product x [W_node_in | W_node_out]^T.  One launch (none when E = 0).
+ * i3d_geomol_edge_bwd: from g = dL/dh [E, H] and the h of the forward (gate h > 0, strict):  dF[j] = g[j] gate [E, H], written
+ *   once;  dPQ [N, 2H]: row v = dP[v] | dQ[v], dP[v] the sum of dF over the out-edges of v in out_ptr / out_epos order, dQ[v] the sum
+ *   over its in-edges in in_ptr order; a zero half-row for a node without such edges.  ONE launch, E = 0 included.
+ * i3d_geomol_residual_fwd: out = (1 + eps[0]) a + b on [rows, H]; eps is a device scalar (edge_eps / node_eps), 1 + eps an fp32
+ *   sum.  One launch (none when rows = 0).
+ * i3d_geomol_residual_bwd: da = (1 + eps[0]) g;  deps[0] = <g, a> accumulated in fp64 per workgroup, the workgroups' partials
+ *   summed in workgroup order and rounded once.  dL/db is g itself.  partials: I3D_GEOMOL_PARTIAL_FLOATS floats, 8-byte aligned.
+ *   Two launches (one when rows = 0: deps = 0). */
+#define I3D_GEOMOL_PARTIAL_FLOATS 2048
+int i3d_geomol_edge_fwd(const float* F, const float* PQ, const int* src_s, const int* dst_s, int num_nodes, int num_edges, int feat,
+                        float* h, void* stream);
+int i3d_geomol_edge_bwd(const float* g, const float* h, const int* in_ptr, const int* out_ptr, const int* out_epos, int num_nodes,
+                        int num_edges, int feat, float* dF, float* dPQ, void* stream);
+int i3d_geomol_residual_fwd(const float* a, const float* b, const float* eps, long rows, int feat, float* out, void* stream);
+int i3d_geomol_residual_bwd(const float* g, const float* a, const float* eps, long rows, int feat, float* partials, float* da,
+                            float* deps, void* stream);
+
 /* ---- local-global NT-Xent: every node embedding against the graph embeddings (reference commons/losses.py:1117-1185;
  * csrc/localglobal.hip) ----
  * zn [n, dim] node embeddings, zg [b, dim] graph embeddings, graph_ptr [b + 1] int32: the nodes of graph j are the rows
