@@ -30,7 +30,7 @@ def __getattr__(name):
     if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
                 'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'NTXentLocalGlobal',
                 'NTXentGlobalLocal', 'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching',
-                'NTXentMaximumSimilarity'):
+                'NTXentMaximumSimilarity', 'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -87,4 +87,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'QM9DenormalizedL1', 'QM9DenormalizedL2', 'QM9SingleTargetDenormalizedL1', 'OGBGNN', 'GNN_node',
            'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal',
            'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity',
-           'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP']
+           'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP',
+           'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled']

@@ -378,6 +378,13 @@ _SIGNATURES = {
     'i3d_conf_match_bwd': (c_int, [_P] * 9 + [c_int, c_int, c_int, c_int, c_int, c_float] + [_P] * 5),
     'i3d_per_conf_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
     'i3d_per_conf_bwd': (c_int, [_P] * 5 + [c_int, c_int, c_int, c_float] + [_P] * 5),
+    'i3d_hardneg_max_extra': (c_int, []),
+    'i3d_hardneg_norms': (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 5),
+    'i3d_hardneg_fwd': (c_int, [c_int] + [_P] * 5 + [c_int] * 4 + [c_double] * 5 + [_P] * 4),
+    'i3d_hardneg_bwd': (c_int, [c_int] + [_P] * 9 + [c_int] * 6 + [c_double] * 3 + [_P] * 8),
+    'i3d_hardneg_loss_scratch_floats': (c_long, [c_int, c_int, c_int]),
+    'i3d_hardneg_loss_fwd': (c_int, [c_int] + [_P] * 3 + [c_int] * 6 + [c_double] * 5 + [_P] * 3),
+    'i3d_hardneg_loss_bwd': (c_int, [c_int] + [_P] * 3 + [c_int] * 6 + [c_double] * 3 + [_P] * 7),
 }
 
 _lib = None

@@ -229,6 +229,11 @@ class _NTXentBase(_Loss):
         return counts
 
     def _contrastive(self, z1, z2, conf):
+        z2, pos_offset, global_batch = self._gathered(z1, z2, conf)
+        return NTXentFn.apply(z1, z2, float(self.tau), float(self._eps), conf, pos_offset, global_batch, bool(self.norm))
+
+    def _gathered(self, z1, z2, conf):
+        """(z2 of the global batch, the column of this rank's first positive, the global batch size)"""
         pos_offset, global_batch = 0, z1.shape[0]
         if self.group is not None:
             import torch.distributed as dist
@@ -243,7 +248,7 @@ class _NTXentBase(_Loss):
                         self._check_equal_shards(z1, dist)
                     z2 = _AllGatherRowsFn.apply(z2, self.group)
                     pos_offset, global_batch = rank * z1.shape[0], world * z1.shape[0]
-        return NTXentFn.apply(z1, z2, float(self.tau), float(self._eps), conf, pos_offset, global_batch, bool(self.norm))
+        return z2, pos_offset, global_batch
 
     def _regularisers(self, loss, z1, z2):
         if self.variance_reg > 0:
@@ -863,3 +868,200 @@ class NTXentGlobalLocal(_Loss):
 
     def forward(self, zg, zn, nodes_per_graph=None, **kwargs) -> Tensor:
         return self.ntxent_local_global(zn, zg, nodes_per_graph)
+
+
+# ---- single-positive losses that re-weight the negatives (csrc/hardneg.hip) -----------------------------------------------------------------
+def _single_positive_shapes(name, z1, z2):
+    """everything that cannot be a batch of these losses is refused before any device work"""
+    if not (torch.is_tensor(z1) and torch.is_tensor(z2)) or z1.dim() != 2 or z2.dim() != 2 or z1.shape[1] != z2.shape[1]:
+        raise ValueError(f'{name}: z1 [batch, dim] and z2 [rows, dim] of one width expected, got '
+                         f'{tuple(z1.shape) if torch.is_tensor(z1) else type(z1).__name__} and '
+                         f'{tuple(z2.shape) if torch.is_tensor(z2) else type(z2).__name__}')
+    if z1.shape[0] < 1 or z1.shape[1] < 1:
+        raise ValueError(f'{name}: z1 of shape {tuple(z1.shape)} holds nothing to contrast')
+
+
+def _device_fp32(name, z1, z2):
+    if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {z1.dtype} and {z2.dtype}')
+    if not (z1.is_cuda and z2.is_cuda):
+        raise RuntimeError(f'{name}: z1 is on {z1.device}, z2 on {z2.device} - the loss runs on the HIP kernels, there is no CPU fallback')
+
+
+class _HardNegFn(torch.autograd.Function):
+    """loss_share = sum_i l_i / global_batch over the local rows of z1, l_i by `mode` (ops.HARDNEG_MODES); one C call per direction.
+    `extra` [b1 U, dim]: the private extra negatives of NTXentExtraNegatives, else None."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, extra, mode, norm, tau, tau_plus, beta, extra_weight, pos_offset, global_batch):
+        z1, z2 = _aligned16(z1), _aligned16(z2)
+        b1, dim = z1.shape
+        b2 = z2.shape[0]
+        n_extra = 0
+        if extra is not None and extra.shape[0] > 0:
+            extra = _aligned16(extra)
+            n_extra = extra.shape[0] // b1
+        else:
+            extra = None
+        L = _lib.load()
+        scratch = torch.empty(L.i3d_hardneg_loss_scratch_floats(b1, b2, n_extra), dtype=torch.float32, device=z1.device)
+        loss = torch.empty(1, dtype=torch.float32, device=z1.device)
+        _lib.check(L.i3d_hardneg_loss_fwd(mode, z1.data_ptr(), z2.data_ptr(), ops._p(extra), b1, b2, n_extra, dim, pos_offset, int(norm),
+                                          tau, tau_plus, beta, extra_weight, 1.0 / global_batch, scratch.data_ptr(), loss.data_ptr(),
+                                          ops._stream()), 'i3d_hardneg_loss_fwd')
+        ctx.cfg = (mode, int(norm), tau, beta, pos_offset, global_batch, n_extra)
+        ctx.has_extra = extra is not None
+        ctx.save_for_backward(*((z1, z2, scratch) + ((extra,) if extra is not None else ())))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mode, norm, tau, beta, pos_offset, global_batch, n_extra = ctx.cfg
+        z1, z2, scratch = ctx.saved_tensors[:3]
+        extra = ctx.saved_tensors[3] if ctx.has_extra else None
+        b1, dim = z1.shape
+        b2 = z2.shape[0]
+        L = _lib.load()
+        work = torch.empty(b1 * b2, dtype=torch.float32, device=z1.device)
+        dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
+        dx = torch.empty_like(extra) if extra is not None else None
+        gs = grad_out.contiguous().float()          # multiplied in on the device: no host read-back
+        _lib.check(L.i3d_hardneg_loss_bwd(mode, z1.data_ptr(), z2.data_ptr(), ops._p(extra), b1, b2, n_extra, dim, pos_offset, norm, tau,
+                                          beta, 1.0 / global_batch, scratch.data_ptr(), gs.data_ptr(), work.data_ptr(), dz1.data_ptr(),
+                                          dz2.data_ptr(), ops._p(dx), ops._stream()), 'i3d_hardneg_loss_bwd')
+        return (dz1, dz2, dx) + (None,) * 8
+
+
+class _SinglePositiveBase(_NTXentBase):
+    """no epsilon in any of them; the data-parallel form is NTXent's: z2 gathered, this rank's share of the global mean returned"""
+    _eps = 0.0
+    _mode = None
+
+    def _loss(self, z1, z2, extra=None, tau_plus=0.0, beta=0.0, extra_weight=1.0):
+        name = type(self).__name__
+        hard = self._mode in ('ntxent_hard', 'infonce_hard')
+        if hard and self._local_world() == 1 and z1.shape[0] == 1:
+            raise ValueError(f'{name}: a global batch of 1 has no negatives to re-weight (the reference takes the mean of an empty tensor)')
+        _device_fp32(name, z1, z2)
+        z2, pos_offset, global_batch = self._gathered(z1, z2, 1)
+        if hard and global_batch == 1:
+            raise ValueError(f'{name}: a global batch of 1 has no negatives to re-weight')
+        return _HardNegFn.apply(z1, z2, extra, ops.HARDNEG_MODES[self._mode], bool(self.norm), float(self.tau), float(tau_plus),
+                                float(beta), float(extra_weight), pos_offset, global_batch)
+
+    def _local_world(self):
+        if self.group is None:
+            return 1
+        import torch.distributed as dist
+        return dist.get_world_size(self.group)
+
+
+class InfoNCE(_SinglePositiveBase):
+    """reference commons/losses.py:998-1034: NTXent with the positive kept in the denominator, l_i = -log(pos_i / sum_j P_ij)."""
+    _mode = 'infonce'
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        _single_positive_shapes(type(self).__name__, z1, z2)
+        return self._regularisers(self._loss(z1, z2), z1, z2)
+
+
+class _HardBase(_SinglePositiveBase):
+    def __init__(self, norm, tau, tau_plus, beta) -> None:
+        super().__init__(norm, tau)
+        self.tau_plus, self.beta = tau_plus, beta
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        _single_positive_shapes(type(self).__name__, z1, z2)
+        return self._loss(z1, z2, tau_plus=self.tau_plus, beta=self.beta)
+
+
+class InfoNCEHard(_HardBase):
+    """reference commons/losses.py:1037-1074: NTXentHard with l_i = -log(pos_i / (pos_i + Ng_i)); no normalisation by default."""
+    _mode = 'infonce_hard'
+
+    def __init__(self, norm: bool = False, tau: float = 0.5, tau_plus=0.1, beta=0.5) -> None:
+        super().__init__(norm, tau, tau_plus, beta)
+
+
+class NTXentHard(_HardBase):
+    """reference commons/losses.py:1077-1114: the negatives re-weighted by P^beta (Robinson et al., Contrastive Learning with Hard
+    Negative Samples), Ng_i = (n sum_j P_ij^(1 + beta) / sum_j P_ij^beta - tau_plus n pos_i) / (1 - tau_plus) clamped from below at
+    n e^(-1 / tau), l_i = -log(pos_i / Ng_i).  The weights are not detached: the gradient runs through them, as in the reference."""
+    _mode = 'ntxent_hard'
+
+    def __init__(self, norm: bool = True, tau: float = 0.5, tau_plus=0.1, beta=0.1) -> None:
+        super().__init__(norm, tau, tau_plus, beta)
+
+
+class _SplitRowsFn(torch.autograd.Function):
+    """x -> (x[:rows], x[rows:]); the backward is one concatenation where torch's two slices launch two zero fills, two copies and an
+    add"""
+
+    @staticmethod
+    def forward(ctx, x, rows):
+        ctx.rows = rows
+        return x[:rows], x[rows:]
+
+    @staticmethod
+    def backward(ctx, g_head, g_tail):
+        return torch.cat([g_head, g_tail]), None
+
+
+class NTXentExtraNegatives(_SinglePositiveBase):
+    """reference commons/losses.py:889-943: z2 is [B (1 + U), dim]; its first B rows are the other view, row B + i U + u is the u-th extra
+    negative of row i alone, weighted by extra_negatives_weight in the denominator.  Data parallel: z2[:B] is gathered, the extras stay
+    local.  The regularisers see z2[:B]."""
+    _mode = 'extra_negatives'
+
+    def __init__(self, norm: bool = True, tau: float = 0.5, uniformity_reg=0, variance_reg=0, covariance_reg=0,
+                 extra_negatives_weight=1) -> None:
+        super().__init__(norm, tau, uniformity_reg, variance_reg, covariance_reg)
+        self.extra_negatives_weight = extra_negatives_weight
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        name = type(self).__name__
+        _single_positive_shapes(name, z1, z2)
+        B = z1.shape[0]
+        if z2.shape[0] < B or z2.shape[0] % B != 0:
+            raise ValueError(f'{name}: the {z2.shape[0]} rows of z2 are not a multiple of the batch size {B} (z2 is [batch * (1 + extra '
+                             'negatives), dim])')
+        U = z2.shape[0] // B - 1
+        if U > ops.HARDNEG_MAX_EXTRA:
+            raise NotImplementedError(f'{name}: {U} extra negatives per row, the kernels are built for 0..{ops.HARDNEG_MAX_EXTRA}')
+        other, extra = _SplitRowsFn.apply(z2, B) if U > 0 else (z2, None)
+        loss = self._loss(z1, other, extra, extra_weight=self.extra_negatives_weight)
+        return self._regularisers(loss, z1, other)
+
+
+class _PermuteRowsFn(torch.autograd.Function):
+    """x[perm] on the device; the backward gathers with the inverse permutation"""
+
+    @staticmethod
+    def forward(ctx, x, perm, inv_perm):
+        ctx.inv_perm = inv_perm
+        return ops.gather_rows(x.contiguous(), perm)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.gather_rows(g.contiguous(), ctx.inv_perm), None, None
+
+
+class NTXentShuffled(_SinglePositiveBase):
+    """reference commons/losses.py:967-995, the control experiment: NT-Xent (no epsilon) against a random permutation of z2, drawn with
+    torch.randperm from the host's default generator as the reference draws it - the same seed gives the same permutation."""
+
+    def __init__(self, norm: bool = True, tau: float = 0.5) -> None:
+        super().__init__(norm, tau)
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        name = type(self).__name__
+        if self._local_world() > 1:
+            raise NotImplementedError(f'{name} on a process group of more than one rank: the permutation would have to be one of the '
+                                      'global batch')
+        _single_positive_shapes(name, z1, z2)
+        _device_fp32(name, z1, z2)
+        perm = torch.randperm(len(z2))
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(len(z2))
+        idx = torch.stack([perm, inv]).to(torch.int32).pin_memory().to(z2.device, non_blocking=True)
+        return self._contrastive(z1, _PermuteRowsFn.apply(z2, idx[0], idx[1]), 1)

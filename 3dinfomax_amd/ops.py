@@ -1105,6 +1105,62 @@ def per_conf_bwd(sim, n1, n2, den, pos, batch, conf, mode, tau, grad_scale_dev):
     return dsim, ca, cb
 
 
+# ---- InfoNCE / NTXentHard / InfoNCEHard / NTXentExtraNegatives (csrc/hardneg.hip) --------------------------------------------------------
+HARDNEG_MODES = {'infonce': 0, 'ntxent_hard': 1, 'infonce_hard': 2, 'extra_negatives': 3}
+HARDNEG_MAX_EXTRA = 256
+
+
+def hardneg_norms(z1, z2, extra=None, norm=True):
+    """-> (n1 [b1], n2 [b2], xdot, xn [b1 U]): the row norms (ones without normalisation) and, one wave per extra negative (i, u) of
+    extra [b1 U, dim], <z1_i, x_iu> and |x_iu| (None without extras)"""
+    _chk(z1)
+    _chk(z2)
+    b1, b2, dev = z1.shape[0], z2.shape[0], z1.device
+    n_extra = 0 if extra is None else _chk(extra).shape[0] // b1
+    n1 = torch.empty(b1, dtype=torch.float32, device=dev)
+    n2 = torch.empty(b2, dtype=torch.float32, device=dev)
+    xdot = torch.empty(b1 * n_extra, dtype=torch.float32, device=dev) if n_extra else None
+    xn = torch.empty(b1 * n_extra, dtype=torch.float32, device=dev) if n_extra else None
+    check(_lib.load().i3d_hardneg_norms(_p(z1), _p(z2), _p(extra) if n_extra else None, b1, b2, n_extra, z1.shape[1], int(bool(norm)),
+                                        _p(n1), _p(n2), _p(xdot), _p(xn), _stream()), 'i3d_hardneg_norms')
+    return n1, n2, xdot, xn
+
+
+def hardneg_fwd(mode, sim, n1, n2, pos_offset, tau, tau_plus=0.0, beta=0.0, extra_weight=1.0, loss_scale=1.0, xdot=None, xn=None):
+    """sim [b1, b2] -> (stats [b1, 5] fp64: pos, S, A, C, l; coef [b1, 4]: cp, c1, c2, cq; loss [1] = loss_scale sum_i l_i)"""
+    _chk(sim)
+    b1, b2 = sim.shape
+    n_extra = 0 if xdot is None else xdot.shape[0] // b1
+    stats = torch.empty(b1, 5, dtype=torch.float64, device=sim.device)
+    coef = torch.empty(b1, 4, dtype=torch.float32, device=sim.device)
+    loss = torch.empty(1, dtype=torch.float32, device=sim.device)
+    check(_lib.load().i3d_hardneg_fwd(int(mode), _p(sim), _p(n1), _p(n2), _p(xdot), _p(xn), b1, b2, n_extra, int(pos_offset), float(tau),
+                                      float(tau_plus), float(beta), float(extra_weight), float(loss_scale), _p(stats), _p(coef),
+                                      _p(loss), _stream()), 'i3d_hardneg_fwd')
+    return stats, coef, loss
+
+
+def hardneg_bwd(mode, sim, n1, n2, coef, z1, z2, pos_offset, tau, beta=0.0, grad_scale=1.0, grad_scale_dev=None, norm=True, extra=None,
+                xdot=None, xn=None):
+    """-> (dsim [b1, b2], ca [b1], cb [b2], dz1 = ca z1 + the extras' part, dz2 = cb z2, dx or None) from one launch; dz1 += dsim z2 and
+    dz2 += dsim^T z1 complete the gradients"""
+    _chk(sim)
+    _chk(z1)
+    _chk(z2)
+    b1, b2 = sim.shape
+    n_extra = 0 if extra is None else _chk(extra).shape[0] // b1
+    dsim = torch.empty_like(sim)
+    ca = torch.empty(b1, dtype=torch.float32, device=sim.device)
+    cb = torch.empty(b2, dtype=torch.float32, device=sim.device)
+    dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
+    dx = torch.empty_like(extra) if n_extra else None
+    check(_lib.load().i3d_hardneg_bwd(int(mode), _p(sim), _p(n1), _p(n2), _p(coef), _p(xdot), _p(xn), _p(z1), _p(z2),
+                                      _p(extra) if n_extra else None, b1, b2, n_extra, z1.shape[1], int(pos_offset), int(bool(norm)),
+                                      float(tau), float(beta), float(grad_scale), _p(grad_scale_dev), _p(dsim), _p(ca), _p(cb), _p(dz1),
+                                      _p(dz2), _p(dx), _stream()), 'i3d_hardneg_bwd')
+    return dsim, ca, cb, dz1, dz2, dx
+
+
 # ---- KLDivergenceMultiplePositives (csrc/klmp.hip) -------------------------------------------------------------------------------------
 def kl_mp_fwd(z1, z2, batch, conf, inv_global_batch, want_loss=True):
     """z1 [B, 2 D] (mean | log-variance), z2 [B C, D] -> (stats [B, 3] fp64: kl_b, sum_d var(z2_b), sum_d exp(s1_b); loss [1] =

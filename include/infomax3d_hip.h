@@ -1383,6 +1383,48 @@ int i3d_per_conf_fwd(const float* sim, const float* n1, const float* n2, int bat
 int i3d_per_conf_bwd(const float* sim, const float* n1, const float* n2, const double* den, const double* pos, int batch, int conf,
                      int mode, float tau, const float* grad_scale, float* dsim, float* ca, float* cb, void* stream);
 
+/* ---- single-positive losses with re-weighted negatives (csrc/hardneg.hip; reference commons/losses.py InfoNCE :998-1034, InfoNCEHard
+ * :1037-1074, NTXentHard :1077-1114, NTXentExtraNegatives :889-943) ----
+ * mode 0 InfoNCE, 1 NTXentHard, 2 InfoNCEHard, 3 NTXentExtraNegatives.  z1 [b1, dim] the local rows, z2 [b2, dim] the (gathered) other
+ * view, the positive of row i is column pos_offset + i; x [b1 n_extra, dim] the private extra negatives of mode 3, row (i, u) at
+ * i n_extra + u, n_extra in 0..i3d_hardneg_max_extra() = 256 (the other modes: 0, x null).  s' = <z1_i, z2_j> / (|z1_i||z2_j|) with no
+ * epsilon (norm == 0: the plain product), P = exp(s' / tau), n = b2 - 1:
+ *   pos_i = P[i, p_i], S_i = sum_{j != p_i} P_ij, A_i = sum_{j != p_i} P_ij^beta, C_i = sum_{j != p_i} P_ij^(1 + beta)
+ *   mode 0: l_i = log(S_i + pos_i) - log pos_i
+ *   mode 1: Ng_i = (n C_i / A_i - tau_plus n pos_i) / (1 - tau_plus), Ngc_i = max(Ng_i, n e^(-1 / tau)), l_i = log Ngc_i - log pos_i
+ *   mode 2: l_i = log(pos_i + Ngc_i) - log pos_i
+ *   mode 3: l_i = log(S_i + extra_weight sum_u Q_iu) - log pos_i, Q_iu = exp(<z1_i, x_iu> / (|z1_i||x_iu|) / tau)
+ * loss[0] = loss_scale sum_i l_i.  The gradient runs through the importance weights P^beta.  mode in 0..3, b1, b2, dim >= 1, tau > 0,
+ * pos_offset + b1 <= b2, modes 1 and 2: b2 >= 2 and tau_plus < 1; anything else returns I3D_ERR_INVALID before a launch.  Rows are read
+ * four floats at a time when their length and the buffers' alignment allow, else one at a time.  Row sums in fp64 in a fixed order, no
+ * atomics.
+ * i3d_hardneg_norms: n1 [b1], n2 [b2] (ones when norm == 0) and, one wave per (i, u), xdot [b1 n_extra] = <z1_i, x_iu>, xn = |x_iu|.
+ * i3d_hardneg_fwd: from sim [b1, b2] = z1 z2^T: stats [b1, 5] (fp64: pos, S, A, C - mode 3: sum_u Q_iu in C's place -, l), coef
+ *   [b1, 4] (cp, c1, c2, cq: dl_i/dP P = cp at the positive, c1 P P^beta + c2 P^beta at a negative, cq Q at an extra negative) and loss.
+ * i3d_hardneg_bwd: one launch: dsim = dL/d sim [b1, b2], the norm-path coefficients ca [b1], cb [b2] (null: not written) and - dz1,
+ *   dz2 non-null - dz1 = ca z1 + the extra negatives' part, dz2 = cb z2, dx [b1 n_extra, dim]; all times grad_scale and
+ *   grad_scale_dev[0] (null: 1).  dz1 += dsim z2 and dz2 += dsim^T z1 complete the gradients.
+ * i3d_hardneg_loss_fwd / _bwd: the whole loss from one call per direction (norms, similarity GEMM, the row pass, the sum; the backward
+ *   launch and the two GEMMs).  scratch: i3d_hardneg_loss_scratch_floats floats, 16-byte aligned, written by _fwd and read by _bwd;
+ *   work: b1 * b2 floats, 16-byte aligned. */
+int i3d_hardneg_max_extra(void);
+int i3d_hardneg_norms(const float* z1, const float* z2, const float* x, int b1, int b2, int n_extra, int dim, int norm, float* n1,
+                      float* n2, float* xdot, float* xn, void* stream);
+int i3d_hardneg_fwd(int mode, const float* sim, const float* n1, const float* n2, const float* xdot, const float* xn, int b1, int b2,
+                    int n_extra, int pos_offset, double tau, double tau_plus, double beta, double extra_weight, double loss_scale,
+                    double* stats, float* coef, float* loss, void* stream);
+int i3d_hardneg_bwd(int mode, const float* sim, const float* n1, const float* n2, const float* coef, const float* xdot, const float* xn,
+                    const float* z1, const float* z2, const float* x, int b1, int b2, int n_extra, int dim, int pos_offset, int norm,
+                    double tau, double beta, double grad_scale, const float* grad_scale_dev, float* dsim, float* ca, float* cb,
+                    float* dz1, float* dz2, float* dx, void* stream);
+long i3d_hardneg_loss_scratch_floats(int b1, int b2, int n_extra);
+int i3d_hardneg_loss_fwd(int mode, const float* z1, const float* z2, const float* x, int b1, int b2, int n_extra, int dim, int pos_offset,
+                         int norm, double tau, double tau_plus, double beta, double extra_weight, double loss_scale, float* scratch,
+                         float* loss, void* stream);
+int i3d_hardneg_loss_bwd(int mode, const float* z1, const float* z2, const float* x, int b1, int b2, int n_extra, int dim, int pos_offset,
+                         int norm, double tau, double beta, double loss_scale, const float* scratch, const float* grad_scale_dev,
+                         float* work, float* dz1, float* dz2, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
