@@ -30,7 +30,8 @@ def __getattr__(name):
     if name in ('NTXent', 'NTXentMultiplePositives', 'NTXentAE', 'NTXentMultiplePositivesSeparate2D', 'NTXentMMDSeparate2D',
                 'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'NTXentLocalGlobal',
                 'NTXentGlobalLocal', 'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching',
-                'NTXentMaximumSimilarity', 'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled'):
+                'NTXentMaximumSimilarity', 'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled',
+                'BarlowTwinsLoss', 'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -88,4 +89,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'GNN_node_Virtualnode', 'GINConv', 'EGNN', 'EGCLayer', 'PNALocal', 'NTXentLocalGlobal', 'NTXentGlobalLocal',
            'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity',
            'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP',
-           'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled']
+           'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled', 'BarlowTwinsLoss',
+           'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss']

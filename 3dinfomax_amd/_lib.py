@@ -385,6 +385,14 @@ _SIGNATURES = {
     'i3d_hardneg_loss_scratch_floats': (c_long, [c_int, c_int, c_int]),
     'i3d_hardneg_loss_fwd': (c_int, [c_int] + [_P] * 3 + [c_int] * 6 + [c_double] * 5 + [_P] * 3),
     'i3d_hardneg_loss_bwd': (c_int, [c_int] + [_P] * 3 + [c_int] * 6 + [c_double] * 3 + [_P] * 7),
+    'i3d_bs_max_repeats': (c_int, []),
+    'i3d_bs_pass_blocks': (c_int, [c_int]),
+    'i3d_bs_moments': (c_int, [_P, _P, c_int, c_int] + [_P] * 6),
+    'i3d_bs_matrix_pass': (c_int, [_P, c_int, c_int] + [c_double] * 4 + [_P, _P]),
+    'i3d_bs_finish': (c_int, [_P, c_int, c_double, _P, c_int, c_int, c_double, _P, _P]),
+    'i3d_bs_col_bwd': (c_int, [_P] * 8 + [c_int, c_int, _P] + [c_double] * 4 + [_P] * 4),
+    'i3d_bs_rows_fwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'i3d_bs_rows_bwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, c_double] + [_P] * 4),
 }
 
 _lib = None

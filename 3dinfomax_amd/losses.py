@@ -1065,3 +1065,185 @@ class NTXentShuffled(_SinglePositiveBase):
         inv[perm] = torch.arange(len(z2))
         idx = torch.stack([perm, inv]).to(torch.int32).pin_memory().to(z2.device, non_blocking=True)
         return self._contrastive(z1, _PermuteRowsFn.apply(z2, idx[0], idx[1]), 1)
+
+
+# ---- the non-contrastive objectives (csrc/batchstat.hip) ------------------------------------------------------------------------------------
+def _shape_of(t):
+    return tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+
+
+def _two_views(name, z1, z2, needs_two_rows):
+    """shapes that cannot be a batch of these losses are refused before any device work"""
+    if not (torch.is_tensor(z1) and torch.is_tensor(z2)) or z1.dim() != 2 or z1.shape != z2.shape:
+        raise ValueError(f'{name}: z1 and z2 [batch, dim] of one shape expected, got {_shape_of(z1)} and {_shape_of(z2)}')
+    if z1.shape[0] < 1 or z1.shape[1] < 1:
+        raise ValueError(f'{name}: z1 of shape {tuple(z1.shape)} holds nothing to compare')
+    if needs_two_rows and z1.shape[0] < 2:
+        raise ValueError(f'{name}: a batch of {z1.shape[0]} has no unbiased variance (the statistics over the batch divide by batch - 1)')
+
+
+def _fp32_on_device(name, *tensors):
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise NotImplementedError(f'{name}: fp32 tensors on the device only, got {t.dtype} on {t.device} (the loss runs on the HIP '
+                                      'kernels, there is no CPU fallback)')
+
+
+class _ColStatFn(torch.autograd.Function):
+    """The terms built on statistics over the batch axis, as one scalar: with barlow = (scale_loss, lambd) the BarlowTwins objective
+    scale_loss (sum_i (C_ii - 1)^2 + lambd sum_{i != j} C_ij^2), C = a1^T a2 / B of the standardised views; var_w (std_loss(z1) +
+    std_loss(z2)); cov_w (cov_loss(z1) + cov_loss(z2)).  One moments launch serves every term; the D x D products are the library's GEMM,
+    and the pass over them leaves their gradient in place, so the backward is GEMMs and one launch."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, barlow, var_w, cov_w):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        n, dim = z1.shape
+        mom, a, c = ops.bs_moments(z1, z2, standardised=barlow is not None, centred=cov_w != 0)
+        count = (1 if barlow is not None else 0) + (2 if cov_w != 0 else 0)
+        partial = torch.empty(count, ops.bs_pass_blocks(dim), dtype=torch.float64, device=z1.device) if count else None
+        saved = [z1, z2, mom]
+        first = 0
+        if barlow is not None:
+            scale_loss, lambd = barlow
+            G = ops.gemm(a[0], a[1], trans_a=True)
+            ops.bs_matrix_pass(G, 1.0 / n, 1.0, scale_loss, scale_loss * lambd, partial[:1])
+            saved += [a[0], a[1], G]
+            first = 1
+        if cov_w != 0:
+            Gc = torch.empty(2, dim, dim, dtype=torch.float32, device=z1.device)
+            for v in range(2):
+                ops.gemm(c[v], c[v], trans_a=True, out=Gc[v])
+            ops.bs_matrix_pass(Gc, 1.0 / (n - 1), 0.0, 0.0, cov_w / dim, partial[first:])
+            saved += [c[0], c[1], Gc]
+        ctx.cfg = (barlow is not None, var_w, cov_w)
+        ctx.save_for_backward(*saved)
+        return ops.bs_finish(partial, 1.0, mom, var_w).reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        has_barlow, var_w, cov_w = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        z1, z2, mom = saved[:3]
+        del saved[:3]
+        n = z1.shape[0]
+        a = da = dc = None
+        if has_barlow:
+            a1, a2, G = saved[:3]
+            del saved[:3]
+            a, da = [a1, a2], [ops.gemm(a2, G, trans_b=True), ops.gemm(a1, G)]          # b G^T, a G
+        if cov_w != 0:
+            c1, c2, Gc = saved[:3]
+            dc = [ops.gemm(c1, Gc[0]), ops.gemm(c2, Gc[1])]                             # G is symmetric: one product per view
+        gs = grad_out.contiguous().float()                                              # multiplied in on the device: no host read-back
+        dz1, dz2 = ops.bs_col_bwd([z1, z2], mom, a, da, dc, sa=1.0 / n, sc=2.0 / (n - 1), var_w=var_w, grad_scale_dev=gs)
+        return dz1, dz2, None, None, None
+
+
+class _RowCosFn(torch.autograd.Function):
+    """mean over rows and repeats of |x / max(|x|, 1e-12) - y_r / max(|y_r|, 1e-12)|^2 for x [B, D] and y [B, D] or [B, D, R] normalised
+    over dim 1; the repeat of x and a transposed y are never built"""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        x, y = x.contiguous(), y.contiguous()
+        rowloss, stats = ops.bs_rows_fwd(x, y)
+        ctx.count = x.shape[0] * (y.shape[2] if y.dim() == 3 else 1)
+        ctx.save_for_backward(x, y, stats)
+        return ops.bs_finish(rowloss, 1.0 / ctx.count).reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y, stats = ctx.saved_tensors
+        return ops.bs_rows_bwd(x, y, stats, 2.0 / ctx.count, grad_out.contiguous().float())
+
+
+class _BatchStatBase(_Loss):
+    """The regularisers of the two-view classes below: variance and covariance terms on the column kernels (their moments computed once
+    per view), the uniformity term the module-level `uniformity_loss`.  No attach_group: under data parallelism the moments and the D x D
+    matrices would have to be all-reduced."""
+
+    def _weights(self):
+        return (float(self.variance_reg) if self.variance_reg > 0 else 0.0, float(self.covariance_reg) if self.covariance_reg > 0 else 0.0)
+
+    def _checked(self, z1, z2, always_two_rows=False):
+        name = type(self).__name__
+        var_w, cov_w = self._weights()
+        _two_views(name, z1, z2, always_two_rows or var_w != 0 or cov_w != 0)
+        _fp32_on_device(name, z1, z2)
+        return var_w, cov_w
+
+    def _uniformity(self, loss, z1, z2):
+        if self.uniformity_reg > 0:
+            loss = loss + self.uniformity_reg * uniformity_loss(z1, z2)
+        return loss
+
+
+class BarlowTwinsLoss(_BatchStatBase):
+    """reference commons/losses.py:45-73 (Zbontar et al., Barlow Twins): both views standardised per column with the unbiased standard
+    deviation, C = z1_norm^T z2_norm / B, loss = scale_loss (sum_i (C_ii - 1)^2 + lambd sum_{i != j} C_ij^2).  No epsilon, as in the
+    reference: a column that is constant over the batch has a standard deviation of 0 and makes the loss non-finite.  A batch of 1 is
+    refused."""
+
+    def __init__(self, scale_loss=1 / 32, lambd=3.9e-3, uniformity_reg=0, variance_reg=0, covariance_reg=0) -> None:
+        super().__init__()
+        self.scale_loss, self.lambd = scale_loss, lambd
+        self.uniformity_reg, self.variance_reg, self.covariance_reg = uniformity_reg, variance_reg, covariance_reg
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        var_w, cov_w = self._checked(z1, z2, always_two_rows=True)
+        loss = _ColStatFn.apply(z1, z2, (float(self.scale_loss), float(self.lambd)), var_w, cov_w)
+        return self._uniformity(loss, z1, z2)
+
+
+class CosineSimilarityLoss(_BatchStatBase):
+    """reference commons/losses.py:76-95 (BYOL, equation 2): mean_i |z1_i / |z1_i| - z2_i / |z2_i||^2 = 2 - 2 mean cos, norms clamped at
+    1e-12 as F.normalize clamps them."""
+
+    def __init__(self, uniformity_reg=0, variance_reg=0, covariance_reg=0) -> None:
+        super().__init__()
+        self.uniformity_reg, self.variance_reg, self.covariance_reg = uniformity_reg, variance_reg, covariance_reg
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        var_w, cov_w = self._checked(z1, z2)
+        loss = _RowCosFn.apply(z1, z2)
+        if var_w != 0 or cov_w != 0:
+            loss = loss + _ColStatFn.apply(z1, z2, None, var_w, cov_w)
+        return self._uniformity(loss, z1, z2)
+
+
+class RegularizationLoss(_BatchStatBase):
+    """reference commons/losses.py:98-123: the mean squared error of the two views plus the variance and covariance terms, which are on
+    by default.  `norm` is accepted and ignored, as in the reference."""
+
+    def __init__(self, norm: bool = True, uniformity_reg=0, variance_reg=1, covariance_reg=0.04) -> None:
+        super().__init__()
+        self.norm = norm
+        self.uniformity_reg, self.variance_reg, self.covariance_reg = uniformity_reg, variance_reg, covariance_reg
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        var_w, cov_w = self._checked(z1, z2)
+        loss = _MSEFn.apply(z1, z2, 1.0)
+        if var_w != 0 or cov_w != 0:
+            loss = loss + _ColStatFn.apply(z1, z2, None, var_w, cov_w)
+        return self._uniformity(loss, z1, z2)
+
+
+class CriticLoss(_Loss):
+    """reference commons/losses.py:33-42: forward(z2, reconstruction) with reconstruction [B, D, R], each of its R vectors (dim 1)
+    normalised and compared with the normalised z2 row: mean over B R of the squared distance.  R = 1 .. 32."""
+
+    def __init__(self) -> None:
+        super().__init__()
+
+    def forward(self, z2, reconstruction, **kwargs) -> Tensor:
+        name = type(self).__name__
+        if (not (torch.is_tensor(z2) and torch.is_tensor(reconstruction)) or z2.dim() != 2 or reconstruction.dim() != 3
+                or tuple(reconstruction.shape[:2]) != tuple(z2.shape) or min(reconstruction.shape) < 1):
+            raise ValueError(f'{name}: z2 [batch, dim] and reconstruction [batch, dim, repeats] expected, got {_shape_of(z2)} and '
+                             f'{_shape_of(reconstruction)}')
+        if reconstruction.shape[2] > ops.BATCHSTAT_MAX_REPEATS:
+            raise NotImplementedError(f'{name}: {reconstruction.shape[2]} repeats, the kernels are built for 1..'
+                                      f'{ops.BATCHSTAT_MAX_REPEATS}')
+        _fp32_on_device(name, z2, reconstruction)
+        return _RowCosFn.apply(z2, reconstruction)

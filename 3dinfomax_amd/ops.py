@@ -1161,6 +1161,86 @@ def hardneg_bwd(mode, sim, n1, n2, coef, z1, z2, pos_offset, tau, beta=0.0, grad
     return dsim, ca, cb, dz1, dz2, dx
 
 
+# ---- BarlowTwinsLoss / CosineSimilarityLoss / RegularizationLoss / CriticLoss (csrc/batchstat.hip) ---------------------------------------
+BATCHSTAT_MAX_REPEATS = 32
+
+
+def bs_moments(z1, z2=None, standardised=False, centred=False):
+    """z [n, dim] -> (mom [views, 2, dim] fp64: column mean and unbiased variance from centred values, [a1, a2] = (z - mean) / std or
+    None, [c1, c2] = z - mean or None); both views in one launch"""
+    views = [_chk(z1)] + ([_chk(z2)] if z2 is not None else [])
+    n, dim = z1.shape
+    mom = torch.empty(len(views), 2, dim, dtype=torch.float64, device=z1.device)
+    a = [torch.empty_like(z) for z in views] if standardised else None
+    c = [torch.empty_like(z) for z in views] if centred else None
+    second = lambda ts: _p(ts[1]) if ts is not None and len(ts) > 1 else None
+    check(_lib.load().i3d_bs_moments(_p(z1), _p(z2), n, dim, _p(a[0]) if a else None, second(a), _p(c[0]) if c else None, second(c),
+                                     _p(mom), _stream()), 'i3d_bs_moments')
+    return mom, a, c
+
+
+def bs_pass_blocks(dim):
+    return _lib.load().i3d_bs_pass_blocks(int(dim))
+
+
+def bs_matrix_pass(m, inv_n, target, w_diag, w_off, partial=None):
+    """m [count, dim, dim] or [dim, dim], C = m inv_n -> partial [count, blocks] fp64, the workgroups' shares of w_diag sum_i
+    (C_ii - target)^2 + w_off sum_{i != j} C_ij^2; m is overwritten with the gradient of that sum with respect to C"""
+    _chk(m)
+    dim = m.shape[-1]
+    count = m.shape[0] if m.dim() == 3 else 1
+    if partial is None:
+        partial = torch.empty(count, bs_pass_blocks(dim), dtype=torch.float64, device=m.device)
+    check(_lib.load().i3d_bs_matrix_pass(_p(m), count, dim, float(inv_n), float(target), float(w_diag), float(w_off), _p(partial),
+                                         _stream()), 'i3d_bs_matrix_pass')
+    return partial
+
+
+def bs_finish(partial, scale=1.0, mom=None, var_w=0.0):
+    """-> loss [1] = scale sum(partial) + var_w * mean over the columns of relu(1 - sqrt(var + 1e-4)), summed over the views of mom"""
+    dev = partial.device if partial is not None else mom.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    views, dim = (mom.shape[0], mom.shape[2]) if mom is not None else (0, 0)
+    check(_lib.load().i3d_bs_finish(_p(partial), partial.numel() if partial is not None else 0, float(scale), _p(mom), views, dim,
+                                    float(var_w) if mom is not None else 0.0, _p(loss), _stream()), 'i3d_bs_finish')
+    return loss
+
+
+def bs_col_bwd(z, mom, a=None, da=None, dc=None, sa=0.0, sc=0.0, var_w=0.0, grad_scale=1.0, grad_scale_dev=None):
+    """z, a, da, dc: lists of one tensor per view ([n, dim]; a / da / dc None: the term is absent) -> [dz per view], the backward of the
+    standardisation, of the centring and of the variance hinge in one launch"""
+    n, dim = z[0].shape
+    dz = [torch.empty_like(_chk(t)) for t in z]
+    at = lambda ts, k: _p(ts[k]) if ts is not None and len(ts) > k else None
+    check(_lib.load().i3d_bs_col_bwd(at(z, 0), at(z, 1), at(a, 0), at(a, 1), at(da, 0), at(da, 1), at(dc, 0), at(dc, 1), n, dim, _p(mom),
+                                     float(sa), float(sc), float(var_w), float(grad_scale), _p(grad_scale_dev), at(dz, 0), at(dz, 1),
+                                     _stream()), 'i3d_bs_col_bwd')
+    return dz
+
+
+def bs_rows_fwd(x, y):
+    """x [rows, dim], y [rows, dim] or [rows, dim, reps] (normalised over dim) -> (rowloss [rows] fp64 = sum_r |x_hat - y_hat_r|^2,
+    stats [rows, 1 + 2 reps] fp64: |x|, |y_r|, <x, y_r>)"""
+    _chk(x)
+    _chk(y)
+    rows, dim = x.shape
+    reps = y.shape[2] if y.dim() == 3 else 1
+    stats = torch.empty(rows, 1 + 2 * reps, dtype=torch.float64, device=x.device)
+    rowloss = torch.empty(rows, dtype=torch.float64, device=x.device)
+    check(_lib.load().i3d_bs_rows_fwd(_p(x), _p(y), rows, dim, reps, _p(stats), _p(rowloss), _stream()), 'i3d_bs_rows_fwd')
+    return rowloss, stats
+
+
+def bs_rows_bwd(x, y, stats, grad_scale, grad_scale_dev=None):
+    """-> (dx, dy) of grad_scale * grad_scale_dev[0] * sum(rowloss) from one launch"""
+    rows, dim = x.shape
+    reps = y.shape[2] if y.dim() == 3 else 1
+    dx, dy = torch.empty_like(x), torch.empty_like(y)
+    check(_lib.load().i3d_bs_rows_bwd(_p(x), _p(y), rows, dim, reps, _p(stats), float(grad_scale), _p(grad_scale_dev), _p(dx), _p(dy),
+                                      _stream()), 'i3d_bs_rows_bwd')
+    return dx, dy
+
+
 # ---- KLDivergenceMultiplePositives (csrc/klmp.hip) -------------------------------------------------------------------------------------
 def kl_mp_fwd(z1, z2, batch, conf, inv_global_batch, want_loss=True):
     """z1 [B, 2 D] (mean | log-variance), z2 [B C, D] -> (stats [B, 3] fp64: kl_b, sum_d var(z2_b), sum_d exp(s1_b); loss [1] =

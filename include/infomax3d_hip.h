@@ -1425,6 +1425,43 @@ int i3d_hardneg_loss_bwd(int mode, const float* z1, const float* z2, const float
                          int norm, double tau, double beta, double loss_scale, const float* scratch, const float* grad_scale_dev,
                          float* work, float* dz1, float* dz2, float* dx, void* stream);
 
+/* ---- the non-contrastive objectives (csrc/batchstat.hip; reference commons/losses.py BarlowTwinsLoss :45-73, CosineSimilarityLoss
+ * :76-95, RegularizationLoss :98-123, CriticLoss :33-42, std_loss / cov_loss :954-964) ----
+ * fp32 in and out; every sum fp64 in a fixed order, no atomics; nothing synchronises with the host.
+ * Column family, z1, z2 [n, dim] (z2 null: one view), n >= 2:
+ * i3d_bs_moments: mom [views, 2, dim] (fp64) = the column means and the unbiased variances sum_i (z_ij - mean_j)^2 / (n - 1), the mean
+ *   first, then the centred squares; a1, a2 (null: not written) = (z - mean) / std with no epsilon, c1, c2 (null: not written) =
+ *   z - mean; both views in one launch of 16-column workgroups.
+ * i3d_bs_matrix_pass: m [count, dim, dim], with C = m inv_n: partial [count, i3d_bs_pass_blocks(dim)] (fp64) = each workgroup's share of
+ *   w_diag sum_i (C_ii - target)^2 + w_off sum_{i != j} C_ij^2, and m is overwritten with G = d(that sum)/dC (w_diag == 0: the diagonal
+ *   is not read into the sum and G_ii = 0).  BarlowTwins: m = a1^T a2, inv_n = 1 / n, target 1, w_diag = scale_loss, w_off = scale_loss
+ *   lambd.  Covariance term: m = c^T c, inv_n = 1 / (n - 1), w_diag = 0, w_off = weight / dim.
+ * i3d_bs_finish: loss[0] = scale sum(partial[0 .. n_partial)) + var_w / dim sum_{view, j} relu(1 - sqrt(var_j + 1e-4)) over mom (var_w
+ *   == 0: mom is not read); one workgroup.
+ * i3d_bs_col_bwd: dz = g [sa (da - colmean(da) - a colsum(da a) / (n - 1)) / std + sc (dc - colmean(dc)) + hc_j (z - mean_j)] for both
+ *   views in one launch; da = a_other G^(T) and dc = c G come from the GEMM (null: the term is absent; BarlowTwins sa = 1 / n, covariance
+ *   sc = 2 / (n - 1) since its G is symmetric), hc_j = -var_w / (dim (n - 1) sqrt(var_j + 1e-4)) where the hinge is active, g =
+ *   grad_scale grad_scale_dev[0] (null: 1).  dz2 null: one view.
+ * Row family, x [rows, dim], y [rows, dim, reps] (element (b, d, r) at (b dim + d) reps + r), reps in 1..i3d_bs_max_repeats() = 32:
+ * i3d_bs_rows_fwd: rowloss [rows] (fp64) = sum_r sum_d (x_d / max(|x|, 1e-12) - y_dr / max(|y_r|, 1e-12))^2, stats [rows, 1 + 2 reps]
+ *   (fp64) = |x|, |y_r|, <x, y_r>; one workgroup per row, y read in memory order.  The mean is i3d_bs_finish with scale = 1 / (rows reps).
+ * i3d_bs_rows_bwd: dx [rows, dim], dy [rows, dim, reps] of grad_scale grad_scale_dev[0] sum_b rowloss_b in one launch; a norm below
+ *   1e-12 keeps the constant denominator (torch F.normalize). */
+int i3d_bs_max_repeats(void);
+int i3d_bs_pass_blocks(int dim);
+int i3d_bs_moments(const float* z1, const float* z2, int n, int dim, float* a1, float* a2, float* c1, float* c2, double* mom,
+                   void* stream);
+int i3d_bs_matrix_pass(float* m, int count, int dim, double inv_n, double target, double w_diag, double w_off, double* partial,
+                       void* stream);
+int i3d_bs_finish(const double* partial, int n_partial, double scale, const double* mom, int views, int dim, double var_w, float* loss,
+                  void* stream);
+int i3d_bs_col_bwd(const float* z1, const float* z2, const float* a1, const float* a2, const float* da1, const float* da2,
+                   const float* dc1, const float* dc2, int n, int dim, const double* mom, double sa, double sc, double var_w,
+                   double grad_scale, const float* grad_scale_dev, float* dz1, float* dz2, void* stream);
+int i3d_bs_rows_fwd(const float* x, const float* y, int rows, int dim, int reps, double* stats, double* rowloss, void* stream);
+int i3d_bs_rows_bwd(const float* x, const float* y, int rows, int dim, int reps, const double* stats, double grad_scale,
+                    const float* grad_scale_dev, float* dx, float* dy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
