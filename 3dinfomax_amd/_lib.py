@@ -320,8 +320,9 @@ _SIGNATURES = {
     'i3d_ntxent_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P]),
     'i3d_row_axpy': (c_int, [_P, _P, c_int, c_int, _P, _P]),
     'i3d_row_scale': (c_int, [_P, _P, c_int, c_int, _P, _P]),
-    'i3d_contrastive_rowstats': (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_float, _P, _P]),
-    'i3d_cov_rowstats': (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    'i3d_contrastive_metrics_out_doubles': (c_long, [c_int, c_int]),
+    'i3d_contrastive_metrics_work_floats': (c_long, [c_int] * 5),
+    'i3d_contrastive_metrics': (c_int, [_P, _P] + [c_int] * 5 + [c_float] * 3 + [_P, _P, _P]),
     'i3d_complete_graph_build': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'i3d_mha_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
     'i3d_mha_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),

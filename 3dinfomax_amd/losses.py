@@ -131,8 +131,12 @@ def _gram(x, rows):
 # Optional regularisers (weights 0 in every BASELINE config): differentiable torch expressions around the library's GEMM for
 # their matrix products.  Semantics of reference commons/losses.py:946-964.
 def _log_mean_gaussian_potential(x, t):
-    """log of the mean of exp(-t |x_i - x_j|^2) over all unordered pairs i < j"""
+    """log of the mean of exp(-t |x_i - x_j|^2) over all unordered pairs i < j.  The distances come from the Gram matrix of the rows
+    with the column mean removed: they do not depend on a common translation, but g_ii + g_jj - 2 g_ij of the raw rows loses every
+    digit once the mean exceeds the spread (embeddings with an offset, a collapsing batch).  The centring is part of the graph, so
+    autograd carries its adjoint (g - mean(g))."""
     n = x.shape[0]
+    x = x - x.mean(dim=0, keepdim=True)
     sq = (x * x).sum(dim=1)
     d2 = (sq[:, None] + sq[None, :] - 2.0 * _gram(x, True)).clamp_min(0.0)
     iu = torch.triu_indices(n, n, offset=1, device=x.device)

@@ -3,9 +3,13 @@ configs_clean/pre-train_QM9.yml:15-24 lists.
 
 The reference trainer calls every metric separately and `.item()`s each result, every `log_iterations` (= 2) steps
 (trainer/self_supervised_trainer.py:31-50, train.py:255-268): nine chains of small device ops and nine host syncs.
-Here the first metric asked about a pair of embedding tensors computes ALL of them in one device pass (five small GEMMs
-+ two row kernels + column sums, csrc/metrics.hip) and brings them to the host with one copy; the other metric objects
-find the result cached, so the trainer's loop costs one synchronisation.  Same class names, constructor arguments and
+Here the first metric asked about a pair of embedding tensors computes ALL of them in one device pass (one C call,
+csrc/metrics.hip) and brings them to the host with one copy; the other metric objects find the result cached, so the trainer's
+loop costs one synchronisation.  Every statistic comes from CENTRED values - column means in fp64 first, distances from the Gram
+matrices of the centred rows, alignment from the rows' differences, variances and covariances from the centred columns - as in the
+reference (row differences, torch.pdist, cov_loss's centring, torch's two-pass std): embeddings with a common offset, a collapsed
+batch and well-aligned views read as what they are (tests/test_gpu_metrics_edges.py).  The products run with exact fp32
+products whatever ops.set_matmul_precision / ops.set_fp32_products say.  Same class names, constructor arguments and
 call signature; the value comes back as a 0-dim CPU tensor (`.item()` works as in the trainer).  The `pos_mask`
 (local-global losses) variants are outside the scope of this path and raise NotImplementedError.
 
@@ -54,18 +58,32 @@ def _fill(cache, key, x1, x2, vals):
     return vals
 
 
-def _second_moments(L, z, n):
-    """device parts of one [n, D] tensor: [sum of the squared off-diagonal covariances], column sums [D], column sums of squares [D]"""
-    D = z.shape[1]
-    C = ops.gemm(z, z, trans_a=True)               # [D, D] second moments
-    s = ops.colsum(z)
-    cr = torch.empty(D, 2, dtype=torch.float32, device=z.device)
-    _lib.check(L.i3d_cov_rowstats(C.data_ptr(), s.data_ptr(), n, D, cr.data_ptr(), ops._stream()), 'i3d_cov_rowstats')
-    return [ops.colsum(cr)[:1], s, cr[:, 1].contiguous()]
+def _device_pass(z1, z2, pairwise, threshold=0.5, t=2.0, alpha=2.0):
+    """i3d_contrastive_metrics (csrc/metrics.hip) on z1 [B1, D1], z2 [B2, D2] -> (row totals [8], then per view: sum of the squared
+    off-diagonal covariances, column means [D], unbiased column variances [D]), fp64, after the one device-to-host copy"""
+    (B1, D1), (B2, D2) = z1.shape, z2.shape
+    L = _lib.load()
+    work = torch.empty(L.i3d_contrastive_metrics_work_floats(B1, B2, D1, D2, int(pairwise)), dtype=torch.float32, device=z1.device)
+    out = torch.empty(L.i3d_contrastive_metrics_out_doubles(D1, D2), dtype=torch.float64, device=z1.device)
+    _lib.check(L.i3d_contrastive_metrics(z1.data_ptr(), z2.data_ptr(), B1, B2, D1, D2, int(pairwise), float(threshold), float(t),
+                                         float(alpha), work.data_ptr(), out.data_ptr(), ops._stream()), 'i3d_contrastive_metrics')
+    host = out[:10 + 2 * D1 + 2 * D2].cpu().numpy()                                  # the one device-to-host copy
+    o = 10 + 2 * D1
+    return host[:8], (host[8], host[10:10 + D1], host[10 + D1:o]), (host[9], host[o:o + D2], host[o + D2:o + 2 * D2])
 
 
-def _col_std_mean(s, q, n):
-    return float(np.sqrt(np.maximum(q - s * s / n, 0.0) / max(n - 1, 1)).mean())
+def _col_std_mean(var):
+    return float(np.sqrt(var).mean())
+
+
+def _all_mean_std(mean, var, n):
+    """mean and unbiased standard deviation over ALL elements of an [n, D] tensor from its column means and unbiased column variances:
+    sum (x - m)^2 = sum_j [(n - 1) var_j + n (mean_j - m)^2], every term a centred quantity"""
+    cnt = n * mean.shape[0]
+    m = mean.mean()
+    with np.errstate(invalid='ignore', divide='ignore'):     # one element: 0 / 0 = NaN, as torch.std
+        ss = ((n - 1) * var).sum() if n > 1 else 0.0         # (one row: var is NaN, the rows' part is zero)
+        return float(m), float(math.sqrt((ss + n * ((mean - m) ** 2).sum()) / np.float64(cnt - 1)))
 
 
 def _all_metrics(x1, x2, threshold=0.5, t=2.0, alpha=2.0):
@@ -79,43 +97,26 @@ def _all_metrics(x1, x2, threshold=0.5, t=2.0, alpha=2.0):
             raise AssertionError('the metrics run on the HIP device (there is no CPU fallback)')
         B1, D = z1.shape
         B2 = z2.shape[0]
-        if B2 < B1 or z2.shape[1] != D:
+        if B2 < B1 or z2.shape[1] != D:                    # x2 may carry extra "noisy" rows at the end (metrics.py:222)
             raise ValueError(f'incompatible embedding shapes {tuple(z1.shape)} / {tuple(z2.shape)}')
-        L = _lib.load()
-        S = ops.gemm(z1, z2[:B1], trans_b=True)            # x2 may carry extra "noisy" rows at the end (metrics.py:222)
-        G1 = ops.gemm(z1, z1, trans_b=True)
-        G2 = ops.gemm(z2, z2, trans_b=True)
-        rows = torch.empty(B2, 8, dtype=torch.float32, device=z1.device)
-        _lib.check(L.i3d_contrastive_rowstats(S.data_ptr(), G1.data_ptr(), G2.data_ptr(), B1, B2, float(threshold), float(t),
-                                              float(alpha), rows.data_ptr(), ops._stream()), 'i3d_contrastive_rowstats')
-        parts = [ops.colsum(rows)]
-        for z, n in ((z1, B1), (z2, B2)):
-            parts += _second_moments(L, z, n)
-        host = torch.cat([p.reshape(-1) for p in parts]).cpu().double().numpy()     # the one device-to-host copy
-    r = host[:8]
-    o = 8
-    cov1, s1, q1 = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
-    o += 1 + 2 * D
-    cov2, s2, q2 = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
-
-    def all_mean_std(s, q, n):
-        cnt = n * D
-        mean = s.sum() / cnt
-        return float(mean), float(math.sqrt(max(q.sum() - s.sum() ** 2 / cnt, 0.0) / max(cnt - 1, 1)))
+        r, (cov1, mean1, var1), (cov2, mean2, var2) = _device_pass(z1, z2, True, threshold, t, alpha)
 
     tpr = r[2] / B1
     tnr = r[3] / (B1 * (B1 - 1)) if B1 > 1 else float('nan')
     vals = {
-        'positive_similarity': (r[1] / B1 + 1) / 2,
+        'positive_similarity': (r[7] / B1 + 1) / 2,          # F.cosine_similarity's clamped norms (:331); the others: plain norms
         'negative_similarity': ((r[0] - r[1]) / (B1 * (B1 - 1)) + 1) / 2 if B1 > 1 else float('nan'),
-        'true_positive_rate': tpr, 'true_negative_rate': tnr, 'contrastive_accuracy': (tpr + tnr) / 2,
+        'true_positive_rate': tpr, 'true_negative_rate': tnr,
+        # (:303-307 adds the two fp32 quotients: the same rounding here, so that equal counts give the reference's very value)
+        'contrastive_accuracy': (np.float32(tpr) + np.float32(tnr)) / np.float32(2),
         'alignment': r[4] / B1,
         'uniformity': (_log(r[5] / (B1 * (B1 - 1) / 2)) + _log(r[6] / (B2 * (B2 - 1) / 2))) / 2 if B1 > 1 else float('nan'),
-        'batch_variance': _col_std_mean(s1, q1, B1) + _col_std_mean(s2, q2, B2),
+        'batch_variance': _col_std_mean(var1) + _col_std_mean(var2),
         'dimension_covariance': cov1 / D + cov2 / D,
     }
-    vals['mean_pred'], vals['std_pred'] = all_mean_std(s1, q1, B1)
-    vals['mean_targets'], vals['std_targets'] = all_mean_std(s2, q2, B2)
+    vals['mean_pred'], vals['std_pred'] = _all_mean_std(mean1, var1, B1)
+    vals['mean_targets'], vals['std_targets'] = _all_mean_std(mean2, var2, B2)
+    vals = {k: float(v) for k, v in vals.items()}
     return _fill(_cache, key, x1, x2, vals)
 
 
@@ -135,16 +136,11 @@ def _per_tensor_metrics(x1, x2):
             raise AssertionError('the metrics run on the HIP device (there is no CPU fallback)')
         if any(z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1 for z in zs):
             raise ValueError(f'incompatible embedding shapes {tuple(x1.shape)} / {tuple(x2.shape)}')
-        L = _lib.load()
-        parts = [p for z in zs for p in _second_moments(L, z, z.shape[0])]
-        host = torch.cat([p.reshape(-1) for p in parts]).cpu().double().numpy()     # the one device-to-host copy
-    vals, o = {'batch_variance': 0.0, 'dimension_covariance': 0.0}, 0
-    for z in zs:
-        n, D = z.shape
-        cov, s, q = host[o], host[o + 1:o + 1 + D], host[o + 1 + D:o + 1 + 2 * D]
-        o += 1 + 2 * D
-        vals['batch_variance'] += _col_std_mean(s, q, n)
-        vals['dimension_covariance'] += cov / D
+        _, *views = _device_pass(zs[0], zs[1], False)
+    vals = {'batch_variance': 0.0, 'dimension_covariance': 0.0}
+    for z, (cov, _, var) in zip(zs, views):
+        vals['batch_variance'] += _col_std_mean(var)
+        vals['dimension_covariance'] += float(cov / z.shape[1])
     return _fill(_per_tensor_cache, key, x1, x2, vals)
 
 

@@ -1044,15 +1044,23 @@ int i3d_adam_step(const void* chunk_table, int n_chunks, float* steps, int n_ste
 /* ---- contrastive monitoring metrics -------------------------------------------------
  * replaces the nine metric modules of configs_clean/pre-train_QM9.yml:15-24 (reference trainer/metrics.py:161-174,
  * 212-333, 443-463; commons/losses.py:946-959), evaluated every log_iterations steps by
- * trainer/self_supervised_trainer.py:31-50.  Inputs are products computed with i3d_gemm_f32:
- *   S = x1 x2[:B1]^T [B1,B1], G1 = x1 x1^T [B1,B1], G2 = x2 x2^T [B2,B2] (B2 >= B1: "noisy" extra rows), C = X^T X [D,D].
- * i3d_contrastive_rowstats: out[B2, 8] per row i: {sum_j cos_ij, cos_ii, [(cos_ii+1)/2 > threshold],
- *   #{j != i: (cos_ij+1)/2 <= threshold}, |x1_i - x2_i|^alpha, sum_{j>i} exp(-t|x1_i-x1_j|^2), the same for x2, 0}
- *   (cos = S / (|x1_i| |x2_j|); rows >= B1 only carry the x2 term).
- * i3d_cov_rowstats: out[D, 2] per row a of C: {sum_{b != a} ((C_ab - s_a s_b / n)/(n-1))^2, C_aa}, s = column sums. */
-int i3d_contrastive_rowstats(const float* S, const float* G1, const float* G2, int B1, int B2, float threshold, float t,
-                             float alpha, float* out, void* stream);
-int i3d_cov_rowstats(const float* C, const float* colsum, int n, int D, float* out, void* stream);
+ * trainer/self_supervised_trainer.py:31-50.  One call per pair of tensors z1 [B1, D1], z2 [B2, D2]; every statistic from CENTRED
+ * values (column means in fp64 first; pairwise distances from the Gram matrices of the centred rows; alignment and row norms from
+ * the rows themselves; covariance from c^T c), the five products on i3d_gemm_f32_ex pinned to exact fp32 products and one K-slice
+ * whatever i3d_set_matmul_precision / i3d_set_fp32_products say (both are restored before the call returns; as they are process-level,
+ * a GEMM issued by ANOTHER host thread during the call would see the pinned values).  Fixed summation orders, no atomics.
+ * pairwise != 0 (D1 == D2, B2 >= B1: the rows of z2 from B1 on are appended "noisy" samples): all statistics; pairwise == 0: the
+ * per-tensor ones (out[0..7] = 0).  work: i3d_contrastive_metrics_work_floats floats (16-byte aligned).
+ * out (fp64, i3d_contrastive_metrics_out_doubles(D1, D2) doubles):
+ *   [0..7] sums over the rows i of {sum_j cos_ij, cos_ii, [(cos_ii+1)/2 > threshold], #{j != i: (cos_ij+1)/2 <= threshold},
+ *          |z1_i - z2_i|^alpha, sum_{j>i} exp(-t|z1_i-z1_j|^2), the same for z2 (all B2 rows),
+ *          <z1_i, z2_i> / (max(|z1_i|, 1e-8) max(|z2_i|, 1e-8)) (F.cosine_similarity)}, cos = <z1_i, z2_j> / (|z1_i| |z2_j|)
+ *   [8], [9] per view sum_{a != b} (cov_ab)^2, cov = c^T c / (n - 1)
+ *   then mean1 [D1] | var1 [D1] | mean2 [D2] | var2 [D2] (unbiased, from centred squares) | D1 + D2 doubles of scratch. */
+long i3d_contrastive_metrics_out_doubles(int D1, int D2);
+long i3d_contrastive_metrics_work_floats(int B1, int B2, int D1, int D2, int pairwise);
+int i3d_contrastive_metrics(const float* z1, const float* z2, int B1, int B2, int D1, int D2, int pairwise, float threshold, float t,
+                            float alpha, float* work, double* out, void* stream);
 
 /* ---- batch assembly -----------------------------------------------------------------
  * replaces B x QM9Dataset.get_complete_graph (reference datasets/qm9_dataset.py:233-244, :215-217) + dgl.batch

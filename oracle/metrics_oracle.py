@@ -10,8 +10,8 @@ def _cos_matrix(x1, x2):
     return (x1 @ x2.T) / torch.outer(x1.norm(dim=1), x2.norm(dim=1))
 
 
-def positive_similarity(x1, x2):                      # :310-333 (global-global branch)
-    return float(((torch.diagonal(_cos_matrix(x1, x2)) + 1) / 2).mean())
+def positive_similarity(x1, x2):                      # :310-333 (global-global branch): F.cosine_similarity, a zero row counts 0
+    return float(((torch.nn.functional.cosine_similarity(x1, x2[:x1.shape[0]]) + 1) / 2).mean())
 
 
 def negative_similarity(x1, x2):                      # :443-463

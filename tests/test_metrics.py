@@ -1,5 +1,7 @@
 """the contrastive monitoring metrics.  CPU: the oracle against the golden values generated from the
-reference's own trainer/metrics.py.  GPU: the one-pass HIP implementation against the same golden values and the oracle."""
+reference's own trainer/metrics.py.  GPU: the one-pass HIP implementation against the same golden values and the oracle, at the
+tolerance the oracle itself is held to (the values are the reference's fp32 results; tests/test_gpu_metrics_edges.py holds the kernels to
+the fp64 results within max(4 err_ref, 2e-6 relative))."""
 import importlib
 
 import numpy as np
@@ -62,10 +64,10 @@ def test_hip_metrics_match_reference_values(case):
         if key not in z.files:
             continue
         v = m(z1, z2).item()                     # the trainer's call pattern (trainer/self_supervised_trainer.py:49)
-        assert _close(v, float(z[key]), rel=2e-4, floor=2e-6), (key, v, float(z[key]))
+        assert _close(v, float(z[key]), rel=2e-5, floor=2e-6), (key, v, float(z[key]))
     allv = M.contrastive_metrics(z1, z2)
     for name in ('mean_pred', 'std_pred', 'mean_targets', 'std_targets'):
-        assert _close(allv[name], float(z[f'{case}/{name}']), rel=2e-4, floor=2e-6), name
+        assert _close(allv[name], float(z[f'{case}/{name}']), rel=2e-5, floor=2e-6), name
     with pytest.raises(NotImplementedError):
         objs['positive_similarity'](z1, z2, pos_mask=torch.eye(len(z1), device='cuda'))
 
@@ -84,4 +86,4 @@ def test_hip_metrics_share_one_pass_and_track_tensor_versions():
     assert M._cache['values'] is not vals and abs((a - 0.5) + (b - 0.5)) < 1e-5
     ref = MO.all_metrics(z1.cpu(), z2.cpu())
     for k, v in M.contrastive_metrics(z1, z2).items():
-        assert _close(v, ref[k], rel=2e-4, floor=2e-6), k
+        assert _close(v, ref[k], rel=2e-5, floor=2e-6), k
