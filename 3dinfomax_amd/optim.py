@@ -144,35 +144,39 @@ class Adam(torch.optim.Adam):
             return None
         return self._step_general(closure)
 
+    def _torch_step(self):
+        """torch's own step for every parameter, out of the cached path: torch advances the step counters on the device (and skips
+        parameters without gradient, so they may differ afterwards), which no host-side count survives - the tensor lists, the chunk
+        table and the host count all go; the next native launch reads the counters back and applies the _steps_unequal test"""
+        self._lists = None
+        self._merged = None
+        self._native = None
+        self._host_step = None
+        return super().step()
+
     @torch.no_grad()
     def _step_general(self, closure=None):
         if closure is not None:
+            self._host_step = None            # torch steps every counter: the next native launch re-reads them
             return super().step(closure)
         if self._lists is None or len(self._lists) != len(self.param_groups):
-            out = super().step()              # torch initialises the state on its first call
+            out = self._torch_step()          # torch initialises the state on its first call
             self._lists = self._build_lists()
-            self._merged = None
-            self._native = None
-            self._host_step = None
             return out
         work = []
         if any(p.grad is not None for p in self._gradless):
-            self._lists = None
-            return super().step()
+            return self._torch_step()
         for group, lst in zip(self.param_groups, self._lists):
             if lst is None:
                 if any(p.grad is not None for p in group['params']):
-                    self._lists = None
-                    return super().step()
+                    return self._torch_step()
                 continue
             ps = lst[0]
             if lst[4] != len(group['params']) or not self._plain(group):
-                self._lists = None
-                return super().step()
+                return self._torch_step()
             grads = [p.grad for p in ps]
             if any(g is None for g in grads):
-                self._lists = None
-                return super().step()
+                return self._torch_step()
             work.append((group, lst, grads))
         if NATIVE_ADAM and self._steps_flat is not None and self._native_step(work):
             return None
@@ -257,3 +261,4 @@ class Adam(torch.optim.Adam):
         self._lists = None
         self._merged = None
         self._native = None
+        self._host_step = None
