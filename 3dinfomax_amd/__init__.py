@@ -31,7 +31,8 @@ def __getattr__(name):
                 'KLDivergenceMultiplePositives', 'OGBNanLabelBCEWithLogitsLoss', 'OGBNanLabelMSELoss', 'NTXentLocalGlobal',
                 'NTXentGlobalLocal', 'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching',
                 'NTXentMaximumSimilarity', 'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled',
-                'BarlowTwinsLoss', 'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss'):
+                'BarlowTwinsLoss', 'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss', 'NTXentLikelihoodLoss',
+                'JSDMultiplePositivesLoss'):
         from . import losses
         return getattr(losses, name)
     if name == 'DistancePredictor':
@@ -57,7 +58,7 @@ def __getattr__(name):
         return getattr(mol_encoder, name)
     if name in ('PositiveSimilarity', 'NegativeSimilarity', 'ContrastiveAccuracy', 'TrueNegativeRate', 'TruePositiveRate',
                 'Uniformity', 'Alignment', 'BatchVariance', 'DimensionCovariance', 'Conformer3DVariance', 'Conformer2DVariance',
-                'contrastive_metrics'):
+                'PositiveProb', 'NegativeProb', 'contrastive_metrics'):
         from . import metrics
         return getattr(metrics, name)
     if name in ('PearsonR', 'Rsquared', 'MAE', 'MeanPredictorLoss', 'QM9DenormalizedL1', 'QM9DenormalizedL2',
@@ -90,4 +91,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'NTXentMultiplePositivesV2', 'NTXentMultiplePositivesV3', 'NTXentMinimumMatching', 'NTXentMaximumSimilarity',
            'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP',
            'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled', 'BarlowTwinsLoss',
-           'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss']
+           'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss', 'NTXentLikelihoodLoss', 'JSDMultiplePositivesLoss',
+           'PositiveProb', 'NegativeProb']

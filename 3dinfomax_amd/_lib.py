@@ -351,6 +351,12 @@ _SIGNATURES = {
     'i3d_mmd_pair_bwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, c_double] + [_P] * 5),
     'i3d_kl_mp_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P]),
     'i3d_kl_mp_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
+    'i3d_gauss_lik_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_long, c_long, _P, _P]),
+    'i3d_gauss_lik_loss': (c_int, [_P, c_int, c_double, _P, _P, _P]),
+    'i3d_gauss_lik_probs': (c_int, [_P, c_int, _P, _P]),
+    'i3d_gauss_lik_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_long, c_long, _P, _P, c_double, _P, _P, _P, _P, _P]),
+    'i3d_gauss_jsd_fwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    'i3d_gauss_jsd_bwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'i3d_masked_loss_partial_floats': (c_long, [c_int, c_int]),
     'i3d_masked_loss_fwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'i3d_masked_loss_bwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -687,6 +687,113 @@ class KLDivergenceMultiplePositives(_Separate2DBase):
         return self._regularisers(loss, a.view(B, 2, D), b.view(B, C, D))
 
 
+# ---- the Gaussian of the 2D view against every molecule's conformers: [B, B] pair matrices (csrc/gausspair.hip) -------------------------------
+def _gauss_pair_shapes(name, z1, z2, min_conf):
+    """(B, C, D) of z1 [B, 2 D] (mean | log-variance) and z2 [B C, D]; everything else is refused before any device work"""
+    if z1.dim() != 2 or z2.dim() != 2:
+        raise ValueError(f'{name}: z1 [batch, 2 * dim] and z2 [batch * conformers, dim] expected, got {tuple(z1.shape)} and '
+                         f'{tuple(z2.shape)}')
+    B, D = z1.shape[0], z2.shape[1]
+    if D < 1 or z1.shape[1] != 2 * D:
+        raise ValueError(f'{name}: z1 has {z1.shape[1]} columns, a mean and a log-variance of dimension {D} need {2 * D}')
+    if B < 1 or z2.shape[0] < B or z2.shape[0] % B != 0:
+        raise ValueError(f'{name}: the {z2.shape[0]} rows of z2 are not a multiple of the batch size {B}')
+    C = z2.shape[0] // B
+    if C < min_conf:
+        raise ValueError(f'{name}: {C} conformer(s) per molecule - the variance over the conformers needs at least two')
+    if B < 2:
+        raise ValueError(f'{name}: a batch of {B} has no negatives')
+    if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+        raise NotImplementedError(f'{name}: fp32 only, got {z1.dtype} and {z2.dtype}')
+    return B, C, D
+
+
+class _LikelihoodFn(torch.autograd.Function):
+    """mean_i (log sum_{j != i} exp(L_ij / tau) - L_ii / tau), L_ij = the mean density of molecule j's conformers under the Gaussian of
+    molecule i; the backward pass keeps L [B, B] and the row terms and recomputes the densities"""
+
+    @staticmethod
+    def forward(ctx, z1, z2, batch, conf, tau):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        lik = ops.gauss_lik_fwd(z1, z2, batch, conf)
+        rows, loss = ops.gauss_lik_loss(lik, tau)
+        ctx.cfg = (batch, conf, tau)
+        ctx.save_for_backward(z1, z2, lik, rows)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf, tau = ctx.cfg
+        z1, z2, lik, rows = ctx.saved_tensors
+        dz1, dz2 = ops.gauss_lik_bwd(z1, z2, batch, conf, lik, rows, tau, grad_out.contiguous().float())
+        return dz1, dz2, None, None, None
+
+
+class NTXentLikelihoodLoss(_Separate2DBase):
+    """reference commons/losses.py:537-595: z1 [B, 2 D] holds a mean and a log-variance per molecule, z2 [B C, D] the 3D embeddings of its C
+    conformers, molecule major.  L_ij = the mean over conformers and features of the per-dimension normal densities of molecule j's
+    conformers under molecule i's Gaussian; NT-Xent over exp(L / tau), rows i the 2D view.  The negatives are summed directly and the row
+    maximum leaves the exponent, so the loss stays finite where the reference's `row sum - positive` rounds to zero.  `norm` is accepted
+    and unused, as in the reference; C = 1 is valid."""
+
+    def __init__(self, norm: bool = True, tau: float = 0.5, uniformity_reg=0, variance_reg=0, covariance_reg=0,
+                 conformer_variance_reg=0) -> None:
+        super().__init__(norm, tau, uniformity_reg, variance_reg, covariance_reg)
+        self.conformer_variance_reg = conformer_variance_reg
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        name = type(self).__name__
+        B, C, D = _gauss_pair_shapes(name, z1, z2, 1)
+        self._refuse_unsupported()
+        if self.conformer_variance_reg > 0 and C < 2:
+            raise ValueError(f'{name}: conformer_variance_reg > 0 with {C} conformer(s) per molecule - the variance over the conformers '
+                             'needs at least two')
+        loss = _LikelihoodFn.apply(z1, z2, B, C, float(self.tau))
+        z2v = z2.reshape(B, C, D)
+        loss = self._regularisers(loss, z1.reshape(B, 2, D), z2v)
+        if self.conformer_variance_reg > 0:       # the hinge of NTXentMultiplePositives over the conformer axis
+            loss = loss + self.conformer_variance_reg * torch.relu(1.0 - (z2v.var(dim=1) + 1e-4).sqrt()).mean()
+        return loss
+
+
+class _JSDFn(torch.autograd.Function):
+    """-mean_a log(S_aa / sum_{b != a} S_ab), S_ab = KL(N(m2_a, v2_a) || N(m1_b, exp(s1_b))) with the reference's epsilons; the backward
+    pass keeps two numbers per molecule and the row terms, and recomputes the conformer statistics"""
+
+    @staticmethod
+    def forward(ctx, z1, z2, batch, conf):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        astat, rows, loss = ops.gauss_jsd_fwd(z1, z2, batch, conf)
+        ctx.cfg = (batch, conf)
+        ctx.save_for_backward(z1, z2, astat, rows)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        batch, conf = ctx.cfg
+        z1, z2, astat, rows = ctx.saved_tensors
+        dz1, dz2 = ops.gauss_jsd_bwd(z1, z2, batch, conf, astat, rows, grad_out.contiguous().float())
+        return dz1, dz2, None, None
+
+
+class JSDMultiplePositivesLoss(_Separate2DBase):
+    """reference commons/losses.py:317-391: z1 [B, 2 D] (mean | log-variance), z2 [B C, D] molecule major.  S[a, b] = 0.5 (log(prod v2_a +
+    1e-5) - sum s_b - D + sum (exp(s_b) + (m2_a - m1_b)^2) / (v2_a + 1e-5)) with m2 / v2 the conformer mean / unbiased variance of molecule
+    a (rows: the 3D view) - the reference's `kl_similarity2`; the loss is NT-Xent over S itself, not exponentiated: `tau` is accepted
+    and unused, and a negative ratio gives NaN.  `sum s` stands for the reference's log of prod exp(s): the same wherever that product
+    neither overflows nor underflows.  One deliberate deviation: identical conformers (v2 = 0) evaluate the formula; the reference raises
+    there, from MultivariateNormal objects whose values it discards."""
+
+    def forward(self, z1, z2, **kwargs) -> Tensor:
+        B, C, D = _gauss_pair_shapes(type(self).__name__, z1, z2, 2)
+        self._refuse_unsupported()
+        a, b = z1.reshape(2 * B, D), z2
+        if self.norm:
+            a, b = _RowNormalizeFn.apply(a), _RowNormalizeFn.apply(b)
+        loss = _JSDFn.apply(a.reshape(B, 2 * D), b, B, C)
+        return self._regularisers(loss, a.view(B, 2, D), b.view(B, C, D))
+
+
 # ---- fine-tuning on multi-task datasets with missing labels (csrc/task.hip) ---------------------------------------------------------------
 def _masked_loss_shapes(name, pred, target):
     """[B, T] views of pred and target (1-D: [B, 1]); everything else is refused before any device work"""

@@ -16,6 +16,10 @@ call signature; the value comes back as a 0-dim CPU tensor (`.item()` works as i
 The metrics of configs/contrastive_training_multiple_positives_kl_div_loss.yml see z1 [B, 2 D] and z2 [B C, D]: Conformer3DVariance /
 Conformer2DVariance (reference trainer/metrics.py:177-209) share one pass of the KL loss's forward kernel, BatchVariance and
 DimensionCovariance - one term per tensor - the per-tensor part of the pass above; each pair costs one synchronisation.
+
+PositiveProb / NegativeProb (reference trainer/metrics.py:336-395, configs/old_configs/contrastive_training_multiple_positives_
+likelihood_loss.yml) take the same z1 and read z2 conformer major: the forward kernel of NTXentLikelihoodLoss through strides, one
+reduction of its [B, B] matrix, one synchronisation for the pair.
 """
 import math
 import weakref
@@ -172,6 +176,35 @@ def _conformer_metrics(x1, x2, normalize):
     return _fill(_conformer_cache, key, x1, x2, vals)
 
 
+# PositiveProb / NegativeProb: the forward kernel of NTXentLikelihoodLoss (csrc/gausspair.hip) and one reduction of its [B, B] matrix
+_prob_cache = {'key': None, 'values': None, 'x1': None, 'x2': None}
+
+
+def _prob_metrics(x1, x2):
+    """z1 [B, 2 D] (mean | log-variance), z2 [C B, D] CONFORMER major - row r is molecule r % B, conformer r // B (the reference views it
+    as z2.view(-1, B, D).permute(1, 0, 2), unlike the loss): L_ij = the mean density of molecule j's conformers under molecule i's
+    Gaussian; positive_prob = mean_i L_ii, negative_prob = mean_i sum_{j != i} L_ij (a sum over j)"""
+    key = _tensor_key(x1, x2)
+    vals = _cached(_prob_cache, key, x1, x2)
+    if vals is not None:
+        return vals
+    if x1.dim() != 2 or x2.dim() != 2 or x1.shape[0] < 1 or x2.shape[1] < 1 or x1.shape[1] != 2 * x2.shape[1] \
+            or x2.shape[0] < x1.shape[0] or x2.shape[0] % x1.shape[0] != 0:
+        raise ValueError(f'incompatible embedding shapes {tuple(x1.shape)} / {tuple(x2.shape)}: [batch, 2 * dim] and '
+                         '[conformers * batch, dim] expected')
+    B = x1.shape[0]
+    if B < 2:
+        raise ValueError(f'incompatible embedding shapes {tuple(x1.shape)} / {tuple(x2.shape)}: a batch of {B} has no negatives')
+    with torch.no_grad():
+        z1, z2 = x1.detach().float().contiguous(), x2.detach().float().contiguous()
+        if not (z1.is_cuda and z2.is_cuda):
+            raise AssertionError('the metrics run on the HIP device (there is no CPU fallback)')
+        lik = ops.gauss_lik_fwd(z1, z2, B, z2.shape[0] // B, conformer_major=True)
+        host = ops.gauss_lik_probs(lik).cpu().numpy()                               # the one device-to-host copy
+    vals = {'positive_prob': float(host[0]), 'negative_prob': float(host[1])}
+    return _fill(_prob_cache, key, x1, x2, vals)
+
+
 def contrastive_metrics(z2d, z3d, threshold=0.5009, t=2.0, alpha=2.0):
     """All metrics (and the four statistics of SelfSupervisedTrainer.evaluate_metrics, :33-36) as a dict of floats."""
     return dict(_all_metrics(z2d, z3d, threshold, t, alpha))
@@ -292,3 +325,24 @@ class Conformer3DVariance(_ConformerVariance):
 class Conformer2DVariance(_ConformerVariance):
     """reference trainer/metrics.py:195-209: mean of exp(log-variance), the second half of every row of z1."""
     name = 'conformer_2d_variance'
+
+
+class _Prob(nn.Module):
+    name = None
+
+    def forward(self, z1, z2, pos_mask=None):
+        if z1.shape[0] == z2.shape[1] == 2:          # the trainer's dictionary-init call (reference trainer/metrics.py:344)
+            return torch.tensor(float('nan'))
+        return torch.tensor(_prob_metrics(z1, z2)[self.name], dtype=torch.float32)
+
+
+class PositiveProb(_Prob):
+    """reference trainer/metrics.py:336-364: the mean over molecules of the mean density of a molecule's own conformers under its
+    predicted Gaussian."""
+    name = 'positive_prob'
+
+
+class NegativeProb(_Prob):
+    """reference trainer/metrics.py:367-395: the mean over molecules of the SUM over the other molecules of the mean density of their
+    conformers under this molecule's Gaussian."""
+    name = 'negative_prob'

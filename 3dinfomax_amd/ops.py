@@ -1264,6 +1264,77 @@ def kl_mp_bwd(z1, z2, batch, conf, inv_global_batch, grad_scale_dev):
     return dz1, dz2
 
 
+# ---- NTXentLikelihoodLoss / PositiveProb / NegativeProb / JSDMultiplePositivesLoss (csrc/gausspair.hip) -----------------------------------
+def gauss_z2_strides(batch, conf, dim, conformer_major=False):
+    """(molecule stride, conformer stride) in floats of z2 [B C, D]: row j C + c (the losses) or row c B + j (the metrics)"""
+    return (dim, batch * dim) if conformer_major else (conf * dim, dim)
+
+
+def gauss_lik_fwd(z1, z2, batch, conf, conformer_major=False):
+    """z1 [B, 2 D] (mean | log-variance), z2 [B C, D] -> lik [B, B] fp64: the mean over conformers and features of the densities of
+    molecule j's conformers under molecule i's Gaussian"""
+    _chk(z1)
+    _chk(z2)
+    dim = z2.shape[1]
+    ms, cs = gauss_z2_strides(batch, conf, dim, conformer_major)
+    lik = torch.empty(batch, batch, dtype=torch.float64, device=z1.device)
+    check(_lib.load().i3d_gauss_lik_fwd(_p(z1), _p(z2), batch, conf, dim, ms, cs, _p(lik), _stream()), 'i3d_gauss_lik_fwd')
+    return lik
+
+
+def gauss_lik_loss(lik, tau):
+    """-> (rows [B, 2] fp64: log den_i, l_i; loss [1] = mean_i l_i)"""
+    batch = lik.shape[0]
+    rows = torch.empty(batch, 2, dtype=torch.float64, device=lik.device)
+    loss = torch.empty(1, dtype=torch.float32, device=lik.device)
+    check(_lib.load().i3d_gauss_lik_loss(_p(lik), batch, float(tau), _p(rows), _p(loss), _stream()), 'i3d_gauss_lik_loss')
+    return rows, loss
+
+
+def gauss_lik_probs(lik):
+    """-> [2] fp64: mean_i lik_ii, mean_i sum_{j != i} lik_ij"""
+    out = torch.empty(2, dtype=torch.float64, device=lik.device)
+    check(_lib.load().i3d_gauss_lik_probs(_p(lik), lik.shape[0], _p(out), _stream()), 'i3d_gauss_lik_probs')
+    return out
+
+
+def gauss_lik_bwd(z1, z2, batch, conf, lik, rows, tau, grad_scale_dev):
+    """-> (dz1, dz2), z2 molecule major; the upstream scalar gradient grad_scale_dev[0] is multiplied in on the device"""
+    _chk(z1)
+    _chk(z2)
+    dim = z2.shape[1]
+    ms, cs = gauss_z2_strides(batch, conf, dim)
+    grad_lik = torch.empty_like(lik)
+    dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
+    check(_lib.load().i3d_gauss_lik_bwd(_p(z1), _p(z2), batch, conf, dim, ms, cs, _p(lik), _p(rows), float(tau), _p(grad_scale_dev),
+                                        _p(grad_lik), _p(dz1), _p(dz2), _stream()), 'i3d_gauss_lik_bwd')
+    return dz1, dz2
+
+
+def gauss_jsd_fwd(z1, z2, batch, conf):
+    """-> (astat [B, 2], rows [B, 3] fp64, loss [1]); the [B, B] similarity is scratch of the forward pass"""
+    _chk(z1)
+    _chk(z2)
+    dev = z1.device
+    astat = torch.empty(batch, 2, dtype=torch.float64, device=dev)
+    sim = torch.empty(batch, batch, dtype=torch.float64, device=dev)
+    rows = torch.empty(batch, 3, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(_lib.load().i3d_gauss_jsd_fwd(_p(z1), _p(z2), batch, conf, z2.shape[1], _p(astat), _p(sim), _p(rows), _p(loss), _stream()),
+          'i3d_gauss_jsd_fwd')
+    return astat, rows, loss
+
+
+def gauss_jsd_bwd(z1, z2, batch, conf, astat, rows, grad_scale_dev):
+    """-> (dz1, dz2); the upstream scalar gradient grad_scale_dev[0] is multiplied in on the device"""
+    _chk(z1)
+    _chk(z2)
+    dz1, dz2 = torch.empty_like(z1), torch.empty_like(z2)
+    check(_lib.load().i3d_gauss_jsd_bwd(_p(z1), _p(z2), batch, conf, z2.shape[1], _p(astat), _p(rows), _p(grad_scale_dev), _p(dz1),
+                                        _p(dz2), _stream()), 'i3d_gauss_jsd_bwd')
+    return dz1, dz2
+
+
 # ---- fine-tuning: NaN-label losses and task moments (csrc/task.hip) -----------------------------------------------------------------------
 MASKED_LOSS_KINDS = {'bce_with_logits': 0, 'mse': 1}
 

@@ -1230,6 +1230,37 @@ int i3d_kl_mp_fwd(const float* z1, const float* z2, int batch, int conf, int dim
 int i3d_kl_mp_bwd(const float* z1, const float* z2, int batch, int conf, int dim, double inv_global_batch, const float* grad_scale,
                   float* dz1, float* dz2, void* stream);
 
+/* ---- NTXentLikelihoodLoss, PositiveProb / NegativeProb, JSDMultiplePositivesLoss (reference commons/losses.py:537-595, :317-391,
+ * trainer/metrics.py:336-395; csrc/gausspair.hip) ----
+ * z1 [B, 2 D] as above (mean m | log-variance s); B = batch >= 2, D = dim >= 1, C = conf >= 1 (likelihood) or >= 2 (JSD), no upper
+ * limit on C and D; anything else returns I3D_ERR_INVALID before a launch.  Every term in fp64, fixed summation order, no atomics, no
+ * buffer beyond [B, B] doubles.
+ * i3d_gauss_lik_fwd: lik [B, B] (fp64), lik[i, j] = 1 / (C D) sum_{c, d} N(x; m_id, exp(s_id)) with x = z2[j mol_stride + c conf_stride
+ *   + d]: the mean over conformers and features of the per-dimension densities.  z2 holds B C D floats; the strides (in floats) are
+ *   those of the molecule-major layout (C D, D) or of the conformer-major one (D, B D), nothing else.
+ * i3d_gauss_lik_loss: rows [B, 2] (fp64) = per row { log den_i = log sum_{j != i} exp(lik_ij / tau), l_i = log den_i - lik_ii / tau }
+ *   - the negatives are summed directly and the row maximum leaves the exponent -, loss[0] = mean_i l_i.
+ * i3d_gauss_lik_probs: out (2 doubles) = { mean_i lik_ii, mean_i sum_{j != i} lik_ij }.
+ * i3d_gauss_lik_bwd: grad_lik [B, B] (fp64, scratch) = d loss / d lik times grad_scale[0] read on the device (null: 1); dz1 [B, 2 D] and
+ *   dz2 (the layout of z2) from one owner thread per output element, both passes recompute the densities.
+ * i3d_gauss_jsd_fwd: z2 molecule major; m2 / v2 = mean / unbiased variance over the conformers (two-pass, no epsilon).  astat [B, 2] =
+ *   per molecule { product over d of the non-zero v2, number of zero v2 }; sim [B, B], rows a: 3D view, columns b: 2D view,
+ *   sim[a, b] = 0.5 (log(prod_d v2_ad + 1e-5) - sum_d s_bd - D + sum_d (exp(s_bd) + (m2_ad - m1_bd)^2) / (v2_ad + 1e-5));
+ *   rows [B, 3] = { sim_aa, den_a = sum_{b != a} sim_ab, -log(sim_aa / den_a) }; loss[0] = the mean of the last (NaN where the ratio is
+ *   negative).
+ * i3d_gauss_jsd_bwd: dz1 [B, 2 D] and dz2 [B C, D] from astat and rows, times grad_scale[0] read on the device (null: 1). */
+int i3d_gauss_lik_fwd(const float* z1, const float* z2, int batch, int conf, int dim, long mol_stride, long conf_stride, double* lik,
+                      void* stream);
+int i3d_gauss_lik_loss(const double* lik, int batch, double tau, double* rows, float* loss, void* stream);
+int i3d_gauss_lik_probs(const double* lik, int batch, double* out, void* stream);
+int i3d_gauss_lik_bwd(const float* z1, const float* z2, int batch, int conf, int dim, long mol_stride, long conf_stride,
+                      const double* lik, const double* rows, double tau, const float* grad_scale, double* grad_lik, float* dz1,
+                      float* dz2, void* stream);
+int i3d_gauss_jsd_fwd(const float* z1, const float* z2, int batch, int conf, int dim, double* astat, double* sim, double* rows,
+                      float* loss, void* stream);
+int i3d_gauss_jsd_bwd(const float* z1, const float* z2, int batch, int conf, int dim, const double* astat, const double* rows,
+                      const float* grad_scale, float* dz1, float* dz2, void* stream);
+
 /* ---- fine-tuning: NaN-label losses and one-pass task moments (csrc/task.hip) ----
  * pred, target [rows, tasks] row major (fp32), rows >= 1, tasks >= 1; anything else returns I3D_ERR_INVALID before a launch.
  * i3d_masked_loss_fwd: stands for `self.bce_loss(pred[is_labeled], target[is_labeled])` / `self.mse_loss(...)` of reference
