@@ -65,13 +65,16 @@ def __getattr__(name):
                 'QM9SingleTargetDenormalizedL1'):
         from . import task_metrics
         return getattr(task_metrics, name)
+    if name == 'BYOLwrapper':
+        from . import byol
+        return byol.BYOLwrapper
     if name == 'Adam':
         from . import optim
         return optim.Adam
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local', 'geomol'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local', 'geomol', 'byol'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -92,4 +95,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP',
            'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled', 'BarlowTwinsLoss',
            'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss', 'NTXentLikelihoodLoss', 'JSDMultiplePositivesLoss',
-           'PositiveProb', 'NegativeProb']
+           'PositiveProb', 'NegativeProb', 'BYOLwrapper']

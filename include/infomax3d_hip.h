@@ -1041,6 +1041,15 @@ int i3d_adam_chunk_bytes(void);
 int i3d_adam_step(const void* chunk_table, int n_chunks, float* steps, int n_steps, double lr, double beta1, double beta2,
                   double weight_decay, double eps, double bias_correction1, double bias_correction2_sqrt, void* stream);
 
+/* ---- moving average of all teacher parameters of a BYOL wrapper in one launch, in place (csrc/ema.hip; reference
+ * trainer/byol_wrapper.py:38-40).  chunk_table: device array of n_chunks records {float* teacher, const float* student, int n,
+ * int pad} (i3d_ema_chunk_bytes() bytes each, n <= i3d_ema_chunk_elems()).  Per element, with three roundings as in the
+ * reference's expression and no fused multiply-add:  teacher = fl(fl(teacher * decay) + fl(student * one_minus_decay));
+ * the caller passes decay = (float)d and one_minus_decay = (float)(1.0 - d), the subtraction in double. */
+int i3d_ema_chunk_elems(void);
+int i3d_ema_chunk_bytes(void);
+int i3d_ema_update(const void* chunk_table, int n_chunks, float decay, float one_minus_decay, void* stream);
+
 /* ---- contrastive monitoring metrics -------------------------------------------------
  * replaces the nine metric modules of configs_clean/pre-train_QM9.yml:15-24 (reference trainer/metrics.py:161-174,
  * 212-333, 443-463; commons/losses.py:946-959), evaluated every log_iterations steps by
