@@ -4,7 +4,7 @@ PNA(+Net3D)+NT-Xent behind the reference's model_type / model3d_type / loss_func
 The package name starts with a digit, so import it with importlib.import_module('3dinfomax_amd') or through
 the alias module `infomax3d_amd` at the repository root.
 """
-from .graph import (BatchedMolGraph, GraphIndex, NodeDropCollate, as_batched_graph, batch, bond_graph,  # noqa: F401
+from .graph import (BatchedMolGraph, GraphIndex, NodeDropCollate, NoisedCoordinatesCollate, NoisedDistancesCollate, as_batched_graph, batch, bond_graph,  # noqa: F401
                     complete_graph, conformer_collate, contrastive_collate, contrastive_vae_collate, graph_collate,
                     pairwise_distance_collate,
                     s_norm_contrastive_collate, s_norm_graph_collate)
@@ -95,4 +95,4 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'GeomolGNNWrapperOGBFeat', 'GeomolGNNOGBFeat', 'GeomolMetaLayer', 'EdgeModel', 'GeomolNodeModel', 'GeomolMLP',
            'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled', 'BarlowTwinsLoss',
            'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss', 'NTXentLikelihoodLoss', 'JSDMultiplePositivesLoss',
-           'PositiveProb', 'NegativeProb', 'BYOLwrapper']
+           'PositiveProb', 'NegativeProb', 'BYOLwrapper', 'NoisedDistancesCollate', 'NoisedCoordinatesCollate']

@@ -5,7 +5,7 @@ The product path has NO fallback: if the HIP library is missing or a call fails,
 import ctypes
 import os
 import re
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # test hooks (tests/test_gpu_dist.py), behind ONE flag and read ONCE, here: I3D_TESTING=1 makes I3D_TEST_PEER_SELFTEST_FAIL /
@@ -345,6 +345,7 @@ _SIGNATURES = {
     'i3d_mse_bwd': (c_int, [_P, _P, c_long, c_double, _P, _P, _P, _P]),
     'i3d_node_drop_build': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                     POINTER(NodeDropView), c_int, _P]),
+    'i3d_noised_graph_build': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_uint64, c_uint64] + [_P] * 12),
     'i3d_row_normalize_fwd': (c_int, [_P, c_int, c_int, _P, _P, _P]),
     'i3d_row_normalize_bwd': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'i3d_sep2d_max_conformers': (c_int, []),

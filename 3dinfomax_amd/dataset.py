@@ -70,6 +70,15 @@ class FlatMolDataset:
         g2, xyz, graph_ptr_dev, n, bnn = self.assemble_2d(ids, device, pin)
         return [g2], [complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)]
 
+    def assemble_noised(self, ids, device, std, num_noised, mode='distances', seed=0, step=0, pin=False):
+        """-> ([g2d], [g3d of (1 + num_noised) B molecules]) on `device`: the layout NoisedDistancesCollate(std, num_noised)
+        (mode 'distances') / NoisedCoordinatesCollate (mode 'coordinates') return (reference datasets/custom_collate.py:131-152,
+        :160-185), the 3D batch and its noised copies built on the device (noised_complete_graphs_on_device: the noise is a
+        function of (seed, step, copy, element))."""
+        g2, xyz, graph_ptr_dev, n, bnn = self.assemble_2d(ids, device, pin)
+        return [g2], [noised_complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, std, num_noised, mode, seed, step,
+                                                       g2._edge_ptr3)]
+
     def assemble_distance(self, ids, device, pin=False):
         """-> ([g2d, pairwise_indices [2, P], mask [B, maxN]], distances [P, 1]) on `device`: the layout
         `pairwise_distance_collate` returns (reference datasets/custom_collate.py:65-78), with the pairs, their distances and the
@@ -412,12 +421,22 @@ class BatchStream(torch.utils.data.Dataset):
     H2D copies and the device-side complete-graph build (`to_device`).  Item i is batch i of a fixed, seeded sequence.
     `node_drop=r`: the GraphCL baseline's batches instead (NodeDropCollate(r), reference datasets/custom_collate.py:230-263):
     the worker draws both views' removal sets (a numpy generator seeded by (seed, i)) and `to_device` gives
-    ([view 1], [view 2]), built on the device (FlatMolDataset.assemble_nodedrop_host, nodedrop_to_device)."""
+    ([view 1], [view 2]), built on the device (FlatMolDataset.assemble_nodedrop_host, nodedrop_to_device).
+    `noised_3d={'std': s, 'num_noised': U, 'mode': 'distances' | 'coordinates'}`: the noised-3D negatives' batches instead
+    (NoisedDistancesCollate(s, U) / NoisedCoordinatesCollate(s, U), reference datasets/custom_collate.py:131-152, :160-185): the
+    host half is the plain one, and `to_device` builds the 3D batch with its U noised copies on the device
+    (noised_complete_graphs_on_device) with seed = this stream's seed and step = i.  Not together with `node_drop`."""
 
     def __init__(self, flat: 'FlatMolDataset', batch_size: int, steps: int, seed: int = 0, drop_last: bool = True,
-                 node_drop=None):
+                 node_drop=None, noised_3d=None):
+        if noised_3d is not None and node_drop is not None:
+            raise ValueError('BatchStream: noised_3d and node_drop are mutually exclusive (one pre-training scheme per stream)')
         self.flat, self.batch_size, self.steps, self.seed = flat, batch_size, steps, seed
         self.node_drop = node_drop
+        self.noised_3d = None
+        if noised_3d is not None:
+            std, num_noised, mode = _noised_3d_options(noised_3d)
+            self.noised_3d = {'std': std, 'num_noised': num_noised, 'mode': mode}
         self.per_epoch = max(len(flat) // batch_size, 1) if drop_last else -(-len(flat) // batch_size)
 
     def __len__(self):
@@ -429,15 +448,22 @@ class BatchStream(torch.utils.data.Dataset):
         ids = order[k * self.batch_size:(k + 1) * self.batch_size]
         if self.node_drop is not None:
             return self.flat.assemble_nodedrop_host(ids, self.node_drop, rng=np.random.default_rng([self.seed, i]))
-        return self.flat.assemble_host(ids)
+        hb = self.flat.assemble_host(ids)
+        if self.noised_3d is not None:
+            hb['noised_3d'] = dict(self.noised_3d, seed=int(self.seed), step=int(i))
+        return hb
 
     @staticmethod
     def to_device(hb, device):
         """-> ([g2d], [g3d]) on `device` (the tensors of `hb` are pinned when the loader was built with pin_memory=True);
-        ([view 1], [view 2]) for a node-drop batch"""
+        ([view 1], [view 2]) for a node-drop batch; g3d with its noised copies for a noised-3D batch"""
         if 'node_drop' in hb:
             return nodedrop_to_device(hb, device)
         g2, xyz, graph_ptr_dev, n, bnn = host_batch_to_device(hb, device)
+        nz = hb.get('noised_3d')
+        if nz is not None:
+            return [g2], [noised_complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, float(nz['std']), int(nz['num_noised']),
+                                                           str(nz['mode']), int(nz['seed']), int(nz['step']), g2._edge_ptr3)]
         return [g2], [complete_graphs_on_device(xyz, graph_ptr_dev, n, bnn, g2._edge_ptr3)]
 
 
@@ -565,4 +591,71 @@ def complete_graphs_on_device(xyz, graph_ptr_dev, n_atoms_host, bnn, edge_ptr_de
                       int(n_atoms_host.max()) - 1)
     g3 = BatchedMolGraph(ids[:E3], ids[E3:], N, bnn, ndata={}, edata={'d': d}, index=idx3)
     g3.mark_ready()          # everything the 3D batch consists of is enqueued: an independent stream may wait for just this
+    return g3
+
+
+NOISED_MODES = {'distances': 0, 'coordinates': 1}      # I3D_NOISED_DISTANCES / I3D_NOISED_COORDINATES
+
+
+def _noised_3d_options(opts):
+    """(std, num_noised, mode) of a `noised_3d` option dict, checked"""
+    unknown = set(opts) - {'std', 'num_noised', 'mode'}
+    if unknown:
+        raise ValueError(f'noised_3d: unknown keys {sorted(unknown)} (std, num_noised, mode)')
+    std, num_noised, mode = float(opts['std']), int(opts['num_noised']), opts.get('mode', 'distances')
+    if mode not in NOISED_MODES:
+        raise ValueError(f"noised_3d: mode {mode!r}: 'distances' (NoisedDistancesCollate) or 'coordinates' (NoisedCoordinatesCollate)")
+    if num_noised < 0:
+        raise ValueError(f'noised_3d: num_noised {num_noised} < 0')
+    return std, num_noised, mode
+
+
+def noised_complete_graphs_on_device(xyz, graph_ptr_dev, n_atoms_host, bnn, std, num_noised, mode, seed, step,
+                                     edge_ptr_dev=None) -> BatchedMolGraph:
+    """The complete distance graphs of a batch followed by `num_noised` noised copies of the whole batch, built by ONE launch of
+    csrc/noised3d.hip from coordinates [N, 3] on the device: the batched 3D graph of NoisedDistancesCollate (mode 'distances':
+    every directed edge's distance plus std z) or NoisedCoordinatesCollate (mode 'coordinates': distances of the positions plus
+    std z, the noised positions in ndata['x']) - reference datasets/custom_collate.py:131-152, :160-185.  Copy-major: molecule i
+    of copy c is graph c B + i, copy 0 is the clean batch, bitwise what `complete_graphs_on_device` gives (all of it for
+    num_noised = 0).  The noise is the builder's own counter-based stream (Philox4x32-10 keyed by `seed`, counter (element, copy,
+    step); element = the batch's edge id in distances mode, its node id in coordinates mode): equal to the collates' torch.randn
+    in distribution, not in values, and a function of (seed, step, copy, element) alone."""
+    from . import _lib
+    if mode not in NOISED_MODES:
+        raise ValueError(f"noised 3D batch: mode {mode!r}: 'distances' or 'coordinates'")
+    dev = xyz.device
+    U = int(num_noised)
+    B, N = int(n_atoms_host.shape[0]), int(xyz.shape[0])
+    E3 = int((n_atoms_host * (n_atoms_host - 1)).sum())
+    T = 1 + U
+    if U < 0 or T * max(E3, N + 1) > 2 ** 31 - 1:
+        raise ValueError(f'noised 3D batch: (1 + num_noised) x the batch = {T} x ({N} nodes, {E3} edges) does not fit the int32 '
+                         'index arrays')
+    if edge_ptr_dev is None:
+        edge_ptr = np.zeros(B + 1, dtype=np.int32)
+        np.cumsum(n_atoms_host * (n_atoms_host - 1), out=edge_ptr[1:])
+        edge_ptr_d = torch.from_numpy(edge_ptr).to(dev, non_blocking=True)
+    else:
+        edge_ptr_d = edge_ptr_dev
+    tN, tE, tB = T * N, T * E3, T * B
+    ints = torch.empty((tN + 1) + 5 * tE + (tB + 1), dtype=torch.int32, device=dev)
+    in_ptr = ints[:tN + 1]
+    src_s, dst_s, perm, inv_perm, out_epos = [ints[tN + 1 + k * tE:tN + 1 + (k + 1) * tE] for k in range(5)]
+    graph_ptr = ints[tN + 1 + 5 * tE:]
+    ids = torch.empty(2 * tE, dtype=torch.int64, device=dev)
+    d = torch.empty(tE, 1, dtype=torch.float32, device=dev)
+    x = torch.empty(tN, 3, dtype=torch.float32, device=dev) if mode == 'coordinates' else None
+    L = _lib.load()
+    stream = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+    mask = (1 << 64) - 1
+    _lib.check(L.i3d_noised_graph_build(xyz.data_ptr(), graph_ptr_dev.data_ptr(), edge_ptr_d.data_ptr(), B, N, E3, U,
+                                        NOISED_MODES[mode], float(std), int(seed) & mask, int(step) & mask, in_ptr.data_ptr(),
+                                        src_s.data_ptr(), dst_s.data_ptr(), perm.data_ptr(), inv_perm.data_ptr(),
+                                        out_epos.data_ptr(), graph_ptr.data_ptr(), ids[:tE].data_ptr(), ids[tE:].data_ptr(),
+                                        d.data_ptr(), x.data_ptr() if x is not None else None, stream),
+               'i3d_noised_graph_build')
+    idx3 = GraphIndex(tN, tE, tB, in_ptr, perm, src_s, dst_s, in_ptr, out_epos, graph_ptr, inv_perm,
+                      int(n_atoms_host.max()) - 1)
+    g3 = BatchedMolGraph(ids[:tE], ids[tE:], tN, bnn.repeat(T), ndata={} if x is None else {'x': x}, edata={'d': d}, index=idx3)
+    g3.mark_ready()
     return g3

@@ -323,6 +323,78 @@ class NodeDropCollate:
         return [batch(view1)], [batch(view2)]
 
 
+def _distance_key(g3, who):
+    """The edge column the noising collates work on: 'w' where the 3D graph has it (what the reference's collates name),
+    otherwise 'd' (what the reference's datasets and Net3D, and this package's complete_graph, Net3D and EGNN name)."""
+    for key in ('w', 'd'):
+        if key in g3.edata:
+            return key
+    raise KeyError(f"{who}: the 3D graphs carry neither edata['w'] nor edata['d'] (complete_graph(mol) sets 'd')")
+
+
+class _NoisedCollate:
+    def __init__(self, std, num_noised):
+        self.std = std
+        self.num_noised = num_noised
+
+    def _check(self, g3):
+        pass
+
+    def _noised_copy(self, g3, key):
+        raise NotImplementedError
+
+    def __call__(self, batch_items):
+        graphs, graphs3d, *targets = map(list, zip(*batch_items))
+        g3 = batch(graphs3d)
+        key = _distance_key(g3, type(self).__name__)
+        self._check(g3)
+        noised = [g3] + [self._noised_copy(g3, key) for _ in range(self.num_noised)]
+        out = [batch(graphs)], [batch(noised)]
+        if targets:
+            return (*out, torch.stack(*targets).float())
+        return out
+
+
+class NoisedDistancesCollate(_NoisedCollate):
+    """Mirror of reference datasets/custom_collate.py:131-152 (the collate of configs/old_configs/contrastive_training_noised_3d.yml,
+    the producer of NTXentExtraNegatives' z2): items (graph, graph3d[, target]) -> ([batched 2D], [batched 3D of (1 + num_noised) B
+    molecules])[, stacked targets].  The 3D batch is the clean batch followed by num_noised copies of it whose distance column is
+    `w + torch.randn_like(w) * std`, one draw of the whole batched column per copy, in copy order: under the same torch seed the
+    copies are exactly the reference's.  Copy-major: molecule i of copy c is graph c B + i (the order the loss's [B, U, D] view of
+    z2[B:] is paired with in the reference, kept as it is).  No clamp: a noised distance may be negative.
+    The edge key: the reference noises edata['w'], which its own datasets and Net3D do not use (they name the distance 'd'); here
+    'w' is noised when the 3D graphs have it - reference-exact - and otherwise 'd', the column complete_graph, Net3D and EGNN use.
+    Items may be BatchedMolGraphs or DGL-like graphs and are left unmodified.  The fast path that builds the copies on the device
+    from the clean batch's upload is dataset.BatchStream(..., noised_3d={...})."""
+
+    def _noised_copy(self, g3, key):
+        w = g3.edata[key]
+        edata = dict(g3.edata)
+        edata[key] = w + torch.randn_like(w) * self.std
+        return BatchedMolGraph(g3._src, g3._dst, g3._n, g3._bnn, dict(g3.ndata), edata)
+
+
+class NoisedCoordinatesCollate(_NoisedCollate):
+    """Mirror of reference datasets/custom_collate.py:160-185: as NoisedDistancesCollate, but every copy's positions are
+    `x + torch.randn_like(x) * std` (one draw of the batched ndata['x'] per copy, in copy order: the reference's draws under
+    the same torch seed), the copy keeps the noised ndata['x'], and the distance of every edge is recomputed from them
+    (torch.norm(x[src] - x[dst], p=2, dim=-1)[:, None]) into the distance column ('w' when the graphs have it, otherwise 'd': see
+    NoisedDistancesCollate).  The 3D graphs must carry ndata['x'] (complete_graph(mol, coordinates=True))."""
+
+    def _check(self, g3):
+        if 'x' not in g3.ndata:
+            raise ValueError("NoisedCoordinatesCollate needs the atom coordinates in ndata['x'] of the 3D graphs "
+                             "(complete_graph(mol, coordinates=True))")
+
+    def _noised_copy(self, g3, key):
+        x = g3.ndata['x']
+        x = x + torch.randn_like(x) * self.std
+        ndata, edata = dict(g3.ndata), dict(g3.edata)
+        ndata['x'] = x
+        edata[key] = torch.norm(x[g3._src] - x[g3._dst], p=2, dim=-1)[:, None]
+        return BatchedMolGraph(g3._src, g3._dst, g3._n, g3._bnn, ndata, edata)
+
+
 def _snorm_n(graphs):
     """sqrt(1 / n_atoms) per node, [N, 1] (reference datasets/custom_collate.py:45-47, 96-98: the graph-size
     normalisation factor of the original PNA, models/pna_original.py:258-259)."""

@@ -1154,6 +1154,30 @@ int i3d_node_drop_build(const int64_t* src, const int64_t* dst, const int64_t* a
                         int max_atoms, int max_edges, int deg_stride, const I3dNodeDropView* views, int n_views,
                         void* stream);
 
+/* ---- noised-3D negatives (csrc/noised3d.hip) ---------------------------------------------------------------------------
+ * replaces NoisedDistancesCollate / NoisedCoordinatesCollate (reference datasets/custom_collate.py:131-152, :160-185: U deep
+ * copies of the batched 3D graph, each noised, then dgl.batch of the 1 + U graphs) for the complete graphs of a batch: ONE
+ * launch builds the whole (1 + U)-fold batch from the inputs of i3d_complete_graph_build.  Copy-major: molecule g of copy c is
+ * graph c B + g, offset by c N nodes and c E3 edges; copy 0 is the clean batch, bitwise what i3d_complete_graph_build writes.
+ * Outputs, T = 1 + num_noised: in_ptr [T N + 1] (== out_ptr), src_s / dst_s / perm / inv_perm / out_epos int32 [T E3],
+ * graph_ptr_out [T B + 1], src_id / dst_id int64 [T E3], d_id fp32 [T E3] and, in coordinates mode, x_out fp32 [T N, 3] (may
+ * be null otherwise).  Every element is written by exactly one thread; no atomics.
+ * I3D_NOISED_DISTANCES:   d = fl(|x_u - x_v|) + std z(c, e), an independent normal per directed edge, no clamp.
+ * I3D_NOISED_COORDINATES: d = |(x_u + std z(c, u)) - (x_v + std z(c, v))|, one 3-vector per (copy, node); x_out holds the
+ *   noised positions.
+ * z: Philox4x32-10, key = (seed low word, seed high word), counter = (element, copy, step low word, step high word), element =
+ * the clean batch's edge id (distances) or node id (coordinates); u(w) = ((w >> 8) + 0.5) 2^-24 rounded to fp32 (in (0, 1]);
+ * z0 = sqrt(-2 ln u(w0)) cos(2 pi u(w1)), z1 = the sine partner, z2 = sqrt(-2 ln u(w2)) cos(2 pi u(w3)); distances mode takes z0,
+ * coordinates mode (z0, z1, z2).  The stream is this builder's own: equal to torch.randn in distribution, not in values.
+ * A total T E3 or T N + 1 beyond int32 is refused (I3D_ERR_INVALID, "does not fit the int32 index arrays"). */
+#define I3D_NOISED_DISTANCES 0
+#define I3D_NOISED_COORDINATES 1
+int i3d_noised_graph_build(const float* coords, const int* graph_ptr, const int* edge_ptr, int num_graphs, int num_nodes,
+                           int num_edges, int num_noised, int mode, float std_, unsigned long long seed,
+                           unsigned long long step, int* in_ptr, int* src_s, int* dst_s, int* perm, int* inv_perm,
+                           int* out_epos, int* graph_ptr_out, int64_t* src_id, int64_t* dst_id, float* d_id, float* x_out,
+                           void* stream);
+
 /* ---- 3D autoencoder (reference models/net3d_VAE.py, commons/losses.py:165-204; csrc/pairmlp.hip) -------------------
  * The pair head distance_net = FCLayer(2H -> D, ReLU, BatchNorm) -> FCLayer(D -> 1) of reference net3d_VAE.py:116-119
  * (projection_layers=2): softplus(f([h_s | h_d]) + f([h_d | h_s])) per ordered pair, each of the two calls with its own batch
