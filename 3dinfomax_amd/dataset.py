@@ -594,7 +594,7 @@ def complete_graphs_on_device(xyz, graph_ptr_dev, n_atoms_host, bnn, edge_ptr_de
     return g3
 
 
-NOISED_MODES = {'distances': 0, 'coordinates': 1}      # I3D_NOISED_DISTANCES / I3D_NOISED_COORDINATES
+from ._lib import NOISED as NOISED_MODES      # noqa: E402  'distances' / 'coordinates': the header's I3D_NOISED_DISTANCES / I3D_NOISED_COORDINATES
 
 
 def _noised_3d_options(opts):

@@ -16,6 +16,8 @@ from . import layers as _layers
 from .layers import _keeps_pre, _set_workspaces
 
 _SIMPLE_ACTS = (None, 'relu', 'leakyrelu')
+# the in-degree groups / (group, scaler) coefficients that the per-degree tables of I3dGroupedFcArgs hold
+_MAX_GROUPS, _MAX_COEF = _lib.array_len(_lib.GroupedFcArgs, 'group_start'), _lib.array_len(_lib.GroupedFcArgs, 'coef')
 KEEP_LAST_ARGS = None
 
 
@@ -70,7 +72,7 @@ def eligible(h, q, index, qmap, plan, params):
         if not W.is_contiguous() or W.shape[0] % 4 or W.shape[1] % 4:
             return False
     groups = index.degree_groups()[2]
-    if len(groups) > 32 or len(groups) * len(plan.coef[0]) > 128:
+    if len(groups) > _MAX_GROUPS or len(groups) * len(plan.coef[0]) > _MAX_COEF:
         return False
     if q is not None and (not q.is_contiguous() or (qmap is not None and q.shape[0] != qmap.rows)):
         return False

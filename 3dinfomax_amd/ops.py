@@ -755,7 +755,7 @@ def pna_messages_normalized(e, aff):
     return out
 
 
-WGRAD_PLAIN, WGRAD_BN, WGRAD_COMBINE = 0, 1, 2
+WGRAD_PLAIN, WGRAD_BN, WGRAD_COMBINE = (_lib.DEFINES[f'I3D_WGRAD_{k}'] for k in ('PLAIN', 'BN', 'COMBINE'))
 
 
 def wgrad_multi(problems, outputs):
@@ -788,7 +788,7 @@ def wgrad_multi(problems, outputs):
         if d.get('coef') is not None:
             arr = _float_array(d['coef'])
             keep.append(arr)
-            o.coef = arr
+            o.coef = ctypes.addressof(arr)
     dev = problems[0]['A'].device
     check(L.i3d_wgrad_multi(pa, len(problems), oa, len(outputs), _p(_gemm_workspace(dev)), GEMM_WORKSPACE_BYTES, _stream()),
           'i3d_wgrad_multi')
@@ -1471,7 +1471,7 @@ def gate_reduce_bwd(gu, m, w, ws, in_ptr, mean=False):
 
 
 # ---- GeoMol's message-passing step (csrc/geomol.hip) -----------------------------------------------------------------------------
-GEOMOL_PARTIAL_FLOATS = 2048      # I3D_GEOMOL_PARTIAL_FLOATS (include/infomax3d_hip.h)
+GEOMOL_PARTIAL_FLOATS = _lib.DEFINES['I3D_GEOMOL_PARTIAL_FLOATS']
 
 
 def geomol_edge_fwd(F, PQ, src_s, dst_s):

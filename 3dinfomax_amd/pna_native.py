@@ -21,6 +21,8 @@ from . import _lib, ops, streams, tape
 
 NATIVE_MODEL = os.environ.get('I3D_NATIVE_MODEL', '1') != '0'
 _SIMPLE = (None, 'relu', 'leakyrelu')
+# the in-degree groups / (group, scaler) coefficients that the per-degree tables of I3dGroupedFcArgs hold
+_MAX_GROUPS, _MAX_COEF = _lib.array_len(_lib.GroupedFcArgs, 'group_start'), _lib.array_len(_lib.GroupedFcArgs, 'coef')
 
 
 class _Desc:
@@ -80,7 +82,7 @@ def eligible(module, g):
         return False
     groups = idx.degree_groups()[2]
     n_sc = len(module.node_gnn.mp_layers[0].scalers)
-    return len(groups) <= 32 and len(groups) * n_sc <= 128
+    return len(groups) <= _MAX_GROUPS and len(groups) * n_sc <= _MAX_COEF
 
 
 def _structure_ok(module):

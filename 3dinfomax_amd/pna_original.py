@@ -218,7 +218,7 @@ class PNAOriginal(nn.Module):
             # (an eval-mode layer under a tape may still be differentiated: that backward is sequenced by the block path only)
             native = (TOWER_NATIVE and (layer.training or tape.active() is None) and ops.GEMM_WORKSPACE_BYTES > 0
                       and idx.num_edges > 0       # (a batch without bonds: the block path handles E = 0)
-                      and _fold_fits(idx, tw))      # (> 32 distinct in-degrees: the block path has no such table)
+                      and _fold_fits(idx, tw))      # (more in-degree groups than I3dTowerLayerArgs.group_start holds: the block path has no such table)
             if native:
                 if tw.graph_norm and snorm_flat is None:
                     snorm_flat = snorm.reshape(-1).contiguous().float()
@@ -393,7 +393,8 @@ class _TowerStacks:
                 arr[i].src, arr[i].dst, arr[i].rows, arr[i].cols, arr[i].ld_src, arr[i].ld_dst = src_ptr, dst_ptr, rows, cols, lds, ldd
             raw = bytes(arr)[:ctypes.sizeof(_lib.CopyBlock) * len(entries)]
             dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device) if entries else None
-            return dev, len(entries)
+            # (the table lives in DEVICE memory: its address as the I3dCopyBlock pointer the entry point declares; `dev` keeps it alive)
+            return dev, ctypes.cast(dev.data_ptr(), ctypes.POINTER(_lib.CopyBlock)) if entries else None, len(entries)
 
         def entry(block, st, src_of, grads):
             t, off, rows, cols, ld, name, r0, c0 = block
@@ -408,9 +409,9 @@ class _TowerStacks:
         self.other_grad = {}         # id(parameter outside the towers) -> its persistent gradient buffer
 
     def _copy(self, tab, reverse):
-        dev, n = tab
+        _, table, n = tab
         if n:
-            _lib.check(_lib.load().i3d_block_copy(dev.data_ptr(), n, int(reverse), ops._stream()), 'i3d_block_copy')
+            _lib.check(_lib.load().i3d_block_copy(table, n, int(reverse), ops._stream()), 'i3d_block_copy')
 
     def pack(self):
         self._copy(self.t_pack, False)
@@ -502,12 +503,13 @@ def _stacks_for(model):
 
 # I3D_TOWER_NATIVE=0: the stacked layer as five block Functions sequenced from Python instead of one C call per direction
 TOWER_NATIVE = True
+_MAX_GROUPS, _MAX_COEF = _lib.array_len(_lib.TowerLayerArgs, 'group_start'), _lib.array_len(_lib.TowerLayerArgs, 'coef')
 
 
 def _fold_fits(idx, tw):
-    """the per-degree tables of I3dTowerLayerArgs hold 32 in-degree groups / 128 (group, scaler) coefficients"""
+    """the per-degree tables of I3dTowerLayerArgs hold _MAX_GROUPS in-degree groups / _MAX_COEF (group, scaler) coefficients"""
     n = len(idx.degree_groups()[2])
-    return n <= 32 and n * len(tw.scalers) <= 128
+    return n <= _MAX_GROUPS and n * len(tw.scalers) <= _MAX_COEF
 
 
 class _TowerLayerFn(torch.autograd.Function):
