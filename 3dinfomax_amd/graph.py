@@ -247,6 +247,74 @@ def complete_graph(mol, coords=None, coordinates=False) -> BatchedMolGraph:
                            edata={'d': torch.from_numpy(d)})
 
 
+def san_laplacian(mol, self_loops=True):
+    """The [n, n] float32 matrix whose eigen-decomposition is SAN's positional encoding, as torch.linalg.eigh reads it (the lower
+    triangle, mirrored).  The reference's lines as written (datasets/ogbg_dataset_extension.py:115-124 with self_loops, A + I;
+    datasets/qm9_dataset.py:405-409 without): D = diag(colsum A), L = D - A, N = D ** -0.5 and `eye - N * L * N` with N a VECTOR,
+    so both factors scale the columns: entry (i, j) is delta_ij - L_ij / D_j, and eigh takes i >= j of it.  An atom without bonds
+    (self_loops=False) gets D = 1 as in the ogbg lines (the qm9 lines would give NaN)."""
+    n = mol.n_atoms
+    A = torch.zeros(n, n)
+    if mol.src.shape[0]:
+        A[torch.from_numpy(mol.src), torch.from_numpy(mol.dst)] = 1.0
+    if self_loops:
+        A = A + torch.eye(n)
+    D = A.sum(dim=0)
+    L = torch.diag(D) - A
+    D = D + (D == 0)
+    N = D ** -0.5
+    M = torch.eye(n) - N * L * N
+    low = torch.tril(M)
+    return low + torch.tril(M, -1).T
+
+
+def laplacian_pos_enc(mol, num_freq=10, self_loops=True, normalize=True):
+    """SAN's Laplacian positional encoding of one `synth.Molecule`, host only -> float32 [n, num_freq, 2]: (eigenvalue,
+    eigenvector entry) of the num_freq lowest eigenvalues of san_laplacian(mol, self_loops) (torch.linalg.eigh), eigenvalues
+    ascending, the eigenvector matrix row-normalised (F.normalize over the kept eigenvectors; normalize=False: as eigh returns
+    them), NaN-padded when n < num_freq, no sign flip.  Reference datasets/ogbg_dataset_extension.py:108-137 (self_loops=True)
+    and datasets/qm9_dataset.py:403-419 (self_loops=False)."""
+    n = mol.n_atoms
+    eig_vals, eig_vecs = torch.linalg.eigh(san_laplacian(mol, self_loops))
+    keep = eig_vals.argsort()[:num_freq]
+    eig_vals, eig_vecs = eig_vals[keep], eig_vecs[:, keep]
+    eig_vecs = eig_vecs[:, eig_vals.argsort()]
+    if normalize:
+        eig_vecs = torch.nn.functional.normalize(eig_vecs, p=2, dim=1, eps=1e-12)
+    if n < num_freq:
+        eig_vecs = torch.nn.functional.pad(eig_vecs, (0, num_freq - n), value=float('nan'))
+        eig_vals = torch.nn.functional.pad(eig_vals, (0, num_freq - n), value=float('nan'))
+    return torch.stack([eig_vals.unsqueeze(0).repeat(n, 1), eig_vecs], dim=-1)
+
+
+def san_graph(mol, num_freq=10, sign_flip=None, self_loops=True) -> BatchedMolGraph:
+    """SAN's input graph of one molecule (reference datasets/ogbg_dataset_extension.py:60-96): the complete graph without self
+    loops in the reference's edge order (synth.complete_graph_edges); edata['feat'] int64 [E, 3] = the bond features on the real
+    edges, zeros elsewhere; edata['real'] int64 [E] = 1 on the real edges; ndata['feat'] the atom features; ndata['pos_enc']
+    [n, num_freq, 2] = laplacian_pos_enc.  sign_flip: one draw `torch.rand(num_freq) >= 0.5` -> +1 / -1 per eigenvector under the
+    caller's seed, multiplied into the eigenvector entries (the reference draws these signs, :66-68, and then drops them); None /
+    False: no draw."""
+    from .synth import complete_graph_edges
+    n = mol.n_atoms
+    src, dst = complete_graph_edges(n)
+    E = src.shape[0]
+    feat = torch.zeros(E, mol.bond_feat.shape[1], dtype=torch.long)
+    real = torch.zeros(E, dtype=torch.long)
+    if mol.src.shape[0]:
+        s, d = torch.from_numpy(mol.src), torch.from_numpy(mol.dst)
+        pos = s * (n - 1) + d - (d > s).long()
+        feat[pos] = torch.from_numpy(mol.bond_feat)
+        real[pos] = 1
+    pe = laplacian_pos_enc(mol, num_freq, self_loops)
+    if sign_flip:
+        flip = torch.rand(num_freq)
+        flip = torch.where(flip >= 0.5, 1.0, -1.0)
+        pe = torch.stack([pe[:, :, 0], pe[:, :, 1] * flip], dim=-1)
+    return BatchedMolGraph(torch.from_numpy(src), torch.from_numpy(dst), n,
+                           ndata={'feat': torch.from_numpy(mol.atom_feat), 'pos_enc': pe},
+                           edata={'feat': feat, 'real': real})
+
+
 def contrastive_collate(batch_items):
     """Mirror of reference datasets/custom_collate.py:105-114 (items may be BatchedMolGraphs or DGL-like graphs)."""
     graphs, graphs3d, *targets = map(list, zip(*batch_items))

@@ -1470,6 +1470,95 @@ def gate_reduce_bwd(gu, m, w, ws, in_ptr, mean=False):
     return gm, colsum(part_ws), colsum(part_bs)
 
 
+# ---- SAN's edge attention (csrc/san.hip) -------------------------------------------------------------------------------------------
+def san_attn_takes(feat, heads, num_codes):
+    """whether the kernels' lane map covers the shape (include/infomax3d_hip.h: i3d_san_attn_fwd); ValueError on impossible sizes"""
+    rc = _lib.load().i3d_san_attn_takes(feat, heads, num_codes)
+    if rc == _lib.NOT_TAKEN:
+        return False
+    check(rc, 'i3d_san_attn_takes')
+    return True
+
+
+def san_edge_codes(bond_idx, real_in, perm, dims):
+    """-> (codes [E] int32, real [E] uint8 or None): the joint bond code (first column fastest, as edge_codes) and the real flag of
+    every edge position of the destination-sorted order, from bond_idx [E, C] and real_in [E] int64 in edge-id order.  One launch."""
+    _chk(bond_idx, torch.int64)
+    _chk(perm, torch.int32)
+    E, n_cols = bond_idx.shape
+    strides, s = [], 1
+    for d in dims:
+        strides.append(s)
+        s *= d
+    assert len(dims) == n_cols and perm.shape[0] == E
+    codes = torch.empty(E, dtype=torch.int32, device=bond_idx.device)
+    real = None
+    if real_in is not None:
+        real_in = _chk(real_in.contiguous(), torch.int64)
+        assert real_in.shape[0] == E
+        real = torch.empty(E, dtype=torch.uint8, device=bond_idx.device)
+    check(_lib.load().i3d_san_edge_codes(_p(bond_idx), _p(real_in), _p(perm), E, n_cols, int_array(strides), _p(codes), _p(real),
+                                         _stream()), 'i3d_san_edge_codes')
+    return codes, real
+
+
+def _san_blocks(Y, H, full_graph):
+    """the column blocks Q | K | V (| Q_2 | K_2) of the stacked product Y [N, 3H or 5H]"""
+    n = 5 if full_graph else 3
+    assert Y.dim() == 2 and Y.shape[1] == n * H and Y.stride(1) == 1, (Y.shape, Y.stride(), H)
+    blocks = [Y[:, b * H:(b + 1) * H] for b in range(n)]
+    return blocks + [None] * (5 - n)
+
+
+def san_attn_fwd(Y, te, te2, codes, real, in_ptr, src_s, heads, gamma, full_graph):
+    """-> (out [N, H], s [E, nh], z [N, nh]) from the stacked projections Y = Q | K | V (| Q_2 | K_2) [N, 3H or 5H] and the tables
+    te, te2 [V, H]; None when the kernel does not take the shape.  One launch; none at all for N = 0 or E = 0 (zero rows)."""
+    _chk(Y)
+    _chk(te)
+    H = te.shape[1]
+    q, k, v, q2, k2 = _san_blocks(Y, H, full_graph)
+    N, V = Y.shape[0], te.shape[0]
+    E = 0 if codes is None else codes.shape[0]
+    if not san_attn_takes(H, heads, V) or (E and (codes.dtype != torch.int32 or (full_graph and real.dtype != torch.uint8))):
+        return None
+    if full_graph:
+        _chk(te2)
+    out = torch.empty(N, H, dtype=torch.float32, device=Y.device)
+    s = torch.empty(E, heads, dtype=torch.float32, device=Y.device)
+    z = torch.empty(N, heads, dtype=torch.float32, device=Y.device)
+    if N == 0 or E == 0:
+        return out.zero_(), s, z.zero_()
+    assert in_ptr.shape[0] == N + 1 and src_s.shape[0] == E
+    check(_lib.load().i3d_san_attn_fwd(_p(q), _p(k), _p(v), _p(q2), _p(k2), Y.stride(0), _p(te), _p(te2), V, _p(codes), _p(real),
+                                       _p(in_ptr), _p(src_s), N, E, H, heads, int(full_graph), float(gamma), _p(out), _p(s), _p(z),
+                                       _stream()), 'i3d_san_attn_fwd')
+    return out, s, z
+
+
+def san_attn_bwd(g, out, z, s, Y, te, te2, codes, real, index, code_order, code_ptr, heads, gamma, full_graph):
+    """-> (dY [N, 3H or 5H], dte [V, H], dte2 [V, H] or None) from g = dL/dout and what san_attn_fwd returned; `index`: the batch's
+    graph.GraphIndex.  Four launches; none for N = 0 or E = 0 (zero gradients)."""
+    _chk(g)
+    H, V = te.shape[1], te.shape[0]
+    q, k, v, q2, k2 = _san_blocks(Y, H, full_graph)
+    N, E = Y.shape[0], s.shape[0]
+    dY = torch.empty_like(Y)
+    dte = torch.empty_like(te)
+    dte2 = torch.empty_like(te2) if full_graph else None
+    if N == 0 or E == 0:
+        return dY.zero_(), dte.zero_(), dte2.zero_() if full_graph else None
+    dq, dk, dv, dq2, dk2 = _san_blocks(dY, H, full_graph)
+    L = _lib.load()
+    gn = torch.empty(N, H, dtype=torch.float32, device=Y.device)
+    ds = torch.empty(E, heads, dtype=torch.float32, device=Y.device)
+    partials = torch.empty(max(L.i3d_san_attn_bwd_partial_floats(E, H, V), 2), dtype=torch.float32, device=Y.device)
+    check(L.i3d_san_attn_bwd(_p(g), _p(out), _p(z), _p(s), _p(q), _p(k), _p(v), _p(q2), _p(k2), Y.stride(0), _p(te), _p(te2), V, _p(codes),
+                             _p(real), _p(index.in_ptr), _p(index.src_s), _p(index.dst_s), _p(index.out_ptr), _p(index.out_epos),
+                             _p(code_order), _p(code_ptr), N, E, H, heads, int(full_graph), float(gamma), _p(gn), _p(ds), _p(partials),
+                             _p(dq), _p(dk), _p(dv), _p(dq2), _p(dk2), dY.stride(0), _p(dte), _p(dte2), _stream()), 'i3d_san_attn_bwd')
+    return dY, dte, dte2
+
+
 # ---- GeoMol's message-passing step (csrc/geomol.hip) -----------------------------------------------------------------------------
 GEOMOL_PARTIAL_FLOATS = _lib.DEFINES['I3D_GEOMOL_PARTIAL_FLOATS']
 

@@ -1534,6 +1534,43 @@ int i3d_bs_rows_fwd(const float* x, const float* y, int rows, int dim, int reps,
 int i3d_bs_rows_bwd(const float* x, const float* y, int rows, int dim, int reps, const double* stats, double grad_scale,
                     const float* grad_scale_dev, float* dx, float* dy, void* stream);
 
+/* ---- SAN: the edge attention of the spectral-attention baseline (reference models/san.py:111-177; csrc/san.hip) ----
+ * N = num_nodes >= 0, E = num_edges >= 0, H = feat >= 1, nh = heads >= 1 with H % nh == 0, V = num_codes >= 1; anything else returns
+ * I3D_ERR_INVALID before a launch.  The kernels cover dh = H / nh <= 64, nh G <= 512 (G the power of two >= max(dh, 4)) and V <= 256;
+ * every other valid call returns I3D_NOT_TAKEN (i3d_san_attn_takes answers the same without pointers) and the caller composes the
+ * step.  N = 0 returns I3D_OK without a launch.
+ * q, k, v, q2, k2 [N, H] with leading dimension ld (column blocks of one [N, 5H] product); te, te2 [V, H] contiguous: the edge
+ * projections E(e), E_2(e) of every bond-feature combination; codes [E] (i3d_edge_codes) and real [E] (0 / 1) in destination-sorted
+ * order (graph.GraphIndex).  full_graph == 0: every edge is real with coefficient 1 and q2, k2, te2, real, dq2, dk2, dte2 are ignored.
+ * i3d_san_attn_fwd: s[p, a] = sum_{d in head a} Ksel_src[d] Qsel_dst[d] Tsel[codes[p]][d] / sqrt(dh)  [E, nh] with (k, q, te) on a real
+ *   edge and (k2, q2, te2) on a fake one; w = exp(clamp(s, -5, 5)) coef, coef = 1 / (gamma + 1) real, gamma / (gamma + 1) fake;
+ *   z[i, a] = sum over the in-edges of w  [N, nh];  out[i, d] = sum over the in-edges of w V_src[d] / (z[i, a] + 1e-6)  [N, H]
+ *   contiguous, an exact zero row for a node without in-edges.  One launch, one wave per destination.
+ * i3d_san_attn_bwd: from g = dL/dout [N, H] and the forward's out, z, s: dq, dk, dv, dq2, dk2 [N, H] with leading dimension ldg
+ *   (dk, dk2, dv gathered over the out-edges in out_ptr / out_epos order), dte, dte2 [V, H] summed in fp64 over chunks of
+ *   i3d_san_attn_chunk_edges() positions of the code-sorted edge list (code_order, code_ptr: ops.code_sorted_index), then per code
+ *   over its chunks (four quarters, each in chunk order, then the four in order), a zero row for a code without edges.  No gradient flows through a score outside [-5, 5].  Scratch: gn [N, H],
+ *   ds [E, nh], partials of i3d_san_attn_bwd_partial_floats(E, H, V) floats, 8-byte aligned.  Four launches (three when E = 0); fixed
+ *   summation order, no atomics, no [E, H] buffer in either direction. */
+/* i3d_san_edge_codes: codes[p] = sum_c feat[perm[p], c] strides[c] (int32) and real[p] = real_in[perm[p]] != 0 (uint8) for every edge
+ *   position p of the destination-sorted order; feat [E, n_cols] and real_in [E] int64 in edge-id order, strides a host array,
+ *   n_cols in 1..8; real_in and real both null: no flags.  One launch, none for E = 0. */
+int i3d_san_edge_codes(const int64_t* feat, const int64_t* real_in, const int* perm, int num_edges, int n_cols, const int* strides,
+                       int* codes, unsigned char* real, void* stream);
+int i3d_san_attn_chunk_edges(void);
+int i3d_san_attn_takes(int feat, int heads, int num_codes);
+long i3d_san_attn_bwd_partial_floats(int num_edges, int feat, int num_codes);
+int i3d_san_attn_fwd(const float* q, const float* k, const float* v, const float* q2, const float* k2, int ld, const float* te,
+                     const float* te2, int num_codes, const int* codes, const unsigned char* real, const int* in_ptr,
+                     const int* src_s, int num_nodes, int num_edges, int feat, int heads, int full_graph, float gamma, float* out,
+                     float* s, float* z, void* stream);
+int i3d_san_attn_bwd(const float* g, const float* out, const float* z, const float* s, const float* q, const float* k, const float* v,
+                     const float* q2, const float* k2, int ld, const float* te, const float* te2, int num_codes, const int* codes,
+                     const unsigned char* real, const int* in_ptr, const int* src_s, const int* dst_s, const int* out_ptr,
+                     const int* out_epos, const int* code_order, const int* code_ptr, int num_nodes, int num_edges, int feat,
+                     int heads, int full_graph, float gamma, float* gn, float* ds, float* partials, float* dq, float* dk, float* dv,
+                     float* dq2, float* dk2, int ldg, float* dte, float* dte2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
