@@ -6,7 +6,7 @@ the alias module `infomax3d_amd` at the repository root.
 """
 from .graph import (BatchedMolGraph, GraphIndex, NodeDropCollate, laplacian_pos_enc, san_graph, san_laplacian, NoisedCoordinatesCollate, NoisedDistancesCollate, as_batched_graph, batch, bond_graph,  # noqa: F401
                     complete_graph, conformer_collate, contrastive_collate, contrastive_vae_collate, graph_collate,
-                    pairwise_distance_collate,
+                    pairwise_distance_collate, GeometricBatch, pytorch_geometric_collate,
                     s_norm_contrastive_collate, s_norm_graph_collate)
 from . import synth  # noqa: F401
 
@@ -47,6 +47,9 @@ def __getattr__(name):
     if name in ('SAN', 'SAN_NodeLPE', 'GraphTransformerLayer', 'MultiHeadAttentionLayer'):
         from . import san
         return getattr(san, name)
+    if name in ('SMP', 'emb', 'init', 'update_e', 'update_v', 'update_u', 'ResidualLayer', 'dist_emb'):      # the reference's class names
+        from . import smp
+        return getattr(smp, name)
     if name == 'PNALocal':
         from . import pna_local
         return pna_local.PNALocal
@@ -77,7 +80,7 @@ def __getattr__(name):
     if name in ('set_matmul_precision', 'get_matmul_precision', 'set_fp32_products', 'get_fp32_products'):
         from . import ops
         return getattr(ops, name)
-    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local', 'geomol', 'byol', 'san'):
+    if name in ('dataset', 'dist', 'tape', 'streams', 'ops', 'net3d_ae', 'pair_head', 'task_metrics', 'gin', 'egnn', 'pna_local', 'geomol', 'byol', 'san', 'smp'):
         import importlib
         return importlib.import_module('.' + name, __name__)
     raise AttributeError(name)
@@ -99,4 +102,5 @@ __all__ = ['PNA', 'PNAGNN', 'PNALayer', 'PNA_AGGREGATORS', 'PNA_SCALERS', 'PNAOr
            'InfoNCE', 'InfoNCEHard', 'NTXentHard', 'NTXentExtraNegatives', 'NTXentShuffled', 'BarlowTwinsLoss',
            'CosineSimilarityLoss', 'RegularizationLoss', 'CriticLoss', 'NTXentLikelihoodLoss', 'JSDMultiplePositivesLoss',
            'PositiveProb', 'NegativeProb', 'BYOLwrapper', 'NoisedDistancesCollate', 'NoisedCoordinatesCollate', 'SAN', 'SAN_NodeLPE',
-           'GraphTransformerLayer', 'MultiHeadAttentionLayer', 'san_graph', 'laplacian_pos_enc']
+           'GraphTransformerLayer', 'MultiHeadAttentionLayer', 'san_graph', 'laplacian_pos_enc', 'SMP', 'GeometricBatch',
+           'pytorch_geometric_collate']

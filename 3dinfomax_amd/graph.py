@@ -482,6 +482,40 @@ def s_norm_contrastive_collate(batch_items):
     return [batch(graphs), _snorm_n(graphs)], [batch(graphs3d)]
 
 
+class GeometricBatch:
+    """What SMP reads of a torch_geometric Batch of Data(z=..., pos=...) objects: z [N, F] int64, pos [N, 3] fp32, batch [N] int64
+    (the molecule of every atom, non-decreasing) and num_graphs, with .to(device).  Built without PyG."""
+
+    def __init__(self, z, pos, batch, num_graphs):
+        self.z, self.pos, self.batch, self.num_graphs = z, pos, batch, int(num_graphs)
+
+    @classmethod
+    def from_data_list(cls, items):
+        """items: objects with .z and .pos (PyG Data), or synth.Molecule (atom_feat, coords)"""
+        zs = [torch.as_tensor(it.z if hasattr(it, 'z') else it.atom_feat) for it in items]
+        ps = [torch.as_tensor(it.pos if hasattr(it, 'pos') else it.coords, dtype=torch.float32) for it in items]
+        sizes = torch.tensor([p.shape[0] for p in ps], dtype=torch.long)
+        return cls(torch.cat(zs), torch.cat(ps), torch.repeat_interleave(torch.arange(len(items)), sizes), len(items))
+
+    def to(self, device, non_blocking=False):
+        return GeometricBatch(self.z.to(device, non_blocking=non_blocking), self.pos.to(device, non_blocking=non_blocking),
+                              self.batch.to(device, non_blocking=non_blocking), self.num_graphs)
+
+    @property
+    def num_nodes(self):
+        return self.pos.shape[0]
+
+
+def pytorch_geometric_collate(batch_items):
+    """Mirror of reference datasets/custom_collate.py:24-27 (the collate of sphere_net.yml and the SMP_*_conformers configs): items
+    (data, target) -> ([GeometricBatch], targets [B, T]).  Items (graph, data) without a tensor in second place give the pair form of
+    pytorch_geometric3d_contrastive_collate (:117-121, the contrastive SMP config): ([batched graph], [GeometricBatch])."""
+    first, second = map(list, zip(*batch_items))
+    if torch.is_tensor(second[0]):
+        return [GeometricBatch.from_data_list(first)], torch.stack(second).float()
+    return [batch(first)], [GeometricBatch.from_data_list(second)]
+
+
 def as_batched_graph(g) -> BatchedMolGraph:
     """Accept a BatchedMolGraph, or any DGL-like object exposing edges(), number_of_nodes(),
     batch_num_nodes(), ndata, edata (real `dgl.DGLGraph` included).  The frames are shared,

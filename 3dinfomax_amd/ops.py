@@ -1559,6 +1559,121 @@ def san_attn_bwd(g, out, z, s, Y, te, te2, codes, real, index, code_order, code_
     return dY, dte, dte2
 
 
+# ---- SMP / SphereNet: geometry, raw bases, triplet interaction (csrc/smp.hip) ---------------------------------------------------------
+class SmpGeometry:
+    """the radius graph and the triplet lists of one batch (include/infomax3d_hip.h: i3d_smp_radius_fill, i3d_smp_triplet_fill):
+    src, dst, dist [E]; in_ptr [N + 1]; trip_ptr [E + 1], idx_kj, idx_ji [T] grouped by ji; kj_ptr [E + 1], kj_order [T] the same
+    list grouped by kj (a stable sort, so every group keeps the triplet order)"""
+    __slots__ = ('N', 'E', 'T', 'src', 'dst', 'dist', 'in_ptr', 'trip_ptr', 'idx_kj', 'idx_ji', 'kj_ptr', 'kj_order')
+
+
+def _ptr_of(counts):
+    ptr = torch.zeros(counts.shape[0] + 1, dtype=torch.int32, device=counts.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return ptr
+
+
+def smp_geometry(pos, batch, num_graphs, cutoff):
+    """-> SmpGeometry of pos [N, 3] with the non-decreasing molecule index batch [N].  Count launch, cumsum, fill launch, twice; the
+    host reads the two totals E and T and nothing else.  N = 0, E = 0 and T = 0 launch nothing further and give empties."""
+    _chk(pos)
+    N, dev = pos.shape[0], pos.device
+    assert pos.shape == (N, 3) and batch.shape == (N,)
+    L = _lib.load()
+    i32 = dict(dtype=torch.int32, device=dev)
+    mol = batch.to(torch.int32).contiguous()
+    graph_ptr = torch.searchsorted(mol, torch.arange(num_graphs + 1, **i32)).to(torch.int32)
+    geo = SmpGeometry()
+    deg = torch.zeros(N, **i32)
+    check(L.i3d_smp_radius_count(_p(pos), _p(mol), _p(graph_ptr), N, num_graphs, float(cutoff), _p(deg), _stream()), 'i3d_smp_radius_count')
+    geo.in_ptr = _ptr_of(deg)
+    geo.N, geo.E = N, int(geo.in_ptr[-1])
+    geo.src, geo.dst = torch.empty(geo.E, **i32), torch.empty(geo.E, **i32)
+    geo.dist = torch.empty(geo.E, dtype=torch.float32, device=dev)
+    check(L.i3d_smp_radius_fill(_p(pos), _p(mol), _p(graph_ptr), _p(geo.in_ptr), N, num_graphs, geo.E, float(cutoff), _p(geo.src),
+                                _p(geo.dst), _p(geo.dist), _stream()), 'i3d_smp_radius_fill')
+    count = torch.zeros(geo.E, **i32)
+    check(L.i3d_smp_triplet_count(_p(geo.src), _p(geo.dst), _p(geo.in_ptr), geo.E, _p(count), _stream()), 'i3d_smp_triplet_count')
+    geo.trip_ptr = _ptr_of(count)
+    geo.T = int(geo.trip_ptr[-1])
+    geo.idx_kj, geo.idx_ji = torch.empty(geo.T, **i32), torch.empty(geo.T, **i32)
+    check(L.i3d_smp_triplet_fill(_p(geo.src), _p(geo.dst), _p(geo.in_ptr), _p(geo.trip_ptr), geo.E, geo.T, _p(geo.idx_kj), _p(geo.idx_ji),
+                                 _stream()), 'i3d_smp_triplet_fill')
+    if geo.T:
+        order = torch.sort(geo.idx_kj, stable=True)[1]
+        geo.kj_order = order.to(torch.int32)
+        geo.kj_ptr = _ptr_of(torch.bincount(geo.idx_kj, minlength=geo.E))
+    else:
+        geo.kj_order, geo.kj_ptr = torch.empty(0, **i32), torch.zeros(geo.E + 1, **i32)
+    return geo
+
+
+def smp_bases(pos, geo, num_spherical, num_radial, cutoff, zeros, norm, pref):
+    """-> (angle [T], torsion [T], sbf [T, n k], t [T, n n k]) fp32 from the fp64 device tables zeros, norm [n, k] and pref [n n] (smp.py
+    builds them).  Three launches, none for T = 0."""
+    _chk(pos)
+    n, k = num_spherical, num_radial
+    for tab, size in ((zeros, n * k), (norm, n * k), (pref, n * n)):
+        _chk(tab, torch.float64)
+        assert tab.numel() == size
+    f32 = dict(dtype=torch.float32, device=pos.device)
+    angle, torsion = torch.empty(geo.T, **f32), torch.empty(geo.T, **f32)
+    sbf, t = torch.empty(geo.T, n * k, **f32), torch.empty(geo.T, n * n * k, **f32)
+    if geo.T:
+        rbf_ws = torch.empty(geo.E, n * k, dtype=torch.float64, device=pos.device)
+        cbf_ws = torch.empty(geo.T, n * n, dtype=torch.float64, device=pos.device)
+        check(_lib.load().i3d_smp_bases(_p(pos), _p(geo.dist), _p(geo.src), _p(geo.dst), _p(geo.in_ptr), _p(geo.idx_kj), _p(geo.idx_ji),
+                                        geo.E, geo.T, n, k, float(cutoff), _p(zeros), _p(norm), _p(pref), _p(rbf_ws), _p(cbf_ws),
+                                        _p(angle), _p(torsion), _p(sbf), _p(t), _stream()), 'i3d_smp_bases')
+    return angle, torsion, sbf, t
+
+
+def smp_triplets_takes(int_emb, basis_emb):
+    """whether the kernels' lane map covers the shape: int_emb <= 256 (lane c owns the columns c + 64 r, r < 1, 2 or 4) and
+    basis_emb <= 8 (a lane keeps its rows of both weights in registers; 16 columns would spill them); ValueError on impossible sizes"""
+    if int_emb < 1 or basis_emb < 1:
+        raise ValueError(f'smp_triplets_takes: int_emb {int_emb} / basis_emb {basis_emb} below 1')
+    rc = _lib.load().i3d_smp_triplets_takes(int_emb, basis_emb)
+    if rc == _lib.NOT_TAKEN:
+        return False
+    check(rc, 'i3d_smp_triplets_takes')
+    return True
+
+
+def smp_triplets_fwd(x, s8, t8, w1, w2, geo):
+    """out [E, I] = sum over the triplets of every ji edge of x[idx_kj] * (s8 w1^T) * (t8 w2^T); None when the kernels do not take
+    (I, Bs).  One launch; none for E = 0, and T = 0 gives zeros."""
+    for a in (x, s8, t8, w1, w2):
+        _chk(a)
+    (E, I), Bs = x.shape, w1.shape[1]
+    assert E == geo.E and s8.shape == (geo.T, Bs) and t8.shape == (geo.T, Bs) and w1.shape == (I, Bs) and w2.shape == (I, Bs)
+    if not smp_triplets_takes(I, Bs):
+        return None
+    if E == 0 or geo.T == 0:
+        return torch.zeros(E, I, dtype=torch.float32, device=x.device)
+    out = torch.empty(E, I, dtype=torch.float32, device=x.device)
+    check(_lib.load().i3d_smp_triplets_fwd(_p(x), _p(s8), _p(t8), _p(w1), _p(w2), _p(geo.trip_ptr), _p(geo.idx_kj), E, geo.T, I, Bs,
+                                           _p(out), _stream()), 'i3d_smp_triplets_fwd')
+    return out
+
+
+def smp_triplets_bwd(g, x, s8, t8, w1, w2, geo):
+    """-> (dx [E, I], ds8 [T, Bs], dt8 [T, Bs], dw1 [I, Bs], dw2 [I, Bs]) from g = dL/dout.  Four launches; zeros for E = 0 or T = 0."""
+    for a in (g, x, s8, t8, w1, w2):
+        _chk(a)
+    (E, I), Bs = x.shape, w1.shape[1]
+    assert g.shape == x.shape
+    if E == 0 or geo.T == 0:
+        return tuple(torch.zeros_like(a) for a in (x, s8, t8, w1, w2))
+    dx, ds8, dt8, dw1, dw2 = (torch.empty_like(a) for a in (x, s8, t8, w1, w2))
+    L = _lib.load()
+    partials = torch.empty(L.i3d_smp_triplets_bwd_partial_floats(geo.T, I, Bs), dtype=torch.float32, device=x.device)
+    check(L.i3d_smp_triplets_bwd(_p(g), _p(x), _p(s8), _p(t8), _p(w1), _p(w2), _p(geo.trip_ptr), _p(geo.idx_kj), _p(geo.idx_ji),
+                                 _p(geo.kj_ptr), _p(geo.kj_order), E, geo.T, I, Bs, _p(partials), _p(dx), _p(ds8), _p(dt8), _p(dw1),
+                                 _p(dw2), _stream()), 'i3d_smp_triplets_bwd')
+    return dx, ds8, dt8, dw1, dw2
+
+
 # ---- GeoMol's message-passing step (csrc/geomol.hip) -----------------------------------------------------------------------------
 GEOMOL_PARTIAL_FLOATS = _lib.DEFINES['I3D_GEOMOL_PARTIAL_FLOATS']
 

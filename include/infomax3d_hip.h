@@ -1571,6 +1571,55 @@ int i3d_san_attn_bwd(const float* g, const float* out, const float* z, const flo
                      int heads, int full_graph, float gamma, float* gn, float* ds, float* partials, float* dq, float* dk, float* dv,
                      float* dq2, float* dk2, int ldg, float* dte, float* dte2, void* stream);
 
+/* ---- SMP / SphereNet: geometry, raw bases and the triplet interaction (reference models/spherical_message_passing.py,
+ * commons/spherical_encoding.py; csrc/smp.hip) ----
+ * N = num_nodes, B = num_graphs, E = num_edges, T = num_triplets, all >= 0; n = num_spherical in 1..7, k = num_radial in 1..64,
+ * I = int_emb >= 1, Bs = basis_emb >= 1; anything else returns I3D_ERR_INVALID before a launch.  A zero count returns I3D_OK without
+ * a launch wherever nothing is to be written.
+ * pos [N, 3] fp32, mol [N] the molecule of every atom (non-decreasing), graph_ptr [B + 1] the atoms of every molecule.
+ * i3d_smp_radius_count: deg[i] = min(i3d_smp_max_neighbors(), atoms j != i of i's molecule with |pos_i - pos_j|^2 < cutoff^2 in fp32).
+ * i3d_smp_radius_fill: with in_ptr [N + 1] the exclusive prefix sum of deg, the edges j -> i at in_ptr[i].., sources ascending - the
+ *   lowest indices within range when the cap cuts, so j -> i may exist without i -> j -: src, dst [E], dist [E] (differences, squares, sum
+ *   and root in fp64 from the fp32 positions, rounded once).
+ * i3d_smp_triplet_count: count[e] = in-edges (k -> j) of the source j of e = (j -> i) with k != i.
+ * i3d_smp_triplet_fill: with trip_ptr [E + 1] the prefix sum of count: idx_kj[t] the position of (k -> j), idx_ji[t] = e, grouped by e,
+ *   k ascending inside a group - the order of the reference's xyztodat.
+ * i3d_smp_bases: angle, torsion [T] (xyztodat's expressions in fp64, rounded once; the candidate k_n == k of the torsion minimum is set
+ *   to 2 pi, not computed) and the raw bases sbf [T, n k], t [T, n n k] of angle_emb / torsion_emb: no envelope, the real harmonics per
+ *   l as [m = 0, cos m = 1..l, sin m = l..1], flat harmonic f paired with the Bessel order f % n.  zeros, norm [n, k] and pref [n n]
+ *   fp64: the fp32-rounded Bessel zeros, the normalisers from them and the harmonics' prefactors (sqrt 2 folded in for m > 0), built by
+ *   the host.  Bessel functions by series / upward recurrence in fp64.  Scratch: rbf_ws [E, n k], cbf_ws [T, n n] fp64.  Three launches.
+ * Triplet interaction: out[e, c] = sum_{t in group e} x[idx_kj[t], c] (sum_b w1[c, b] s8[t, b]) (sum_b w2[c, b] t8[t, b]) with x [E, I],
+ *   s8, t8 [T, Bs], w1, w2 [I, Bs] contiguous.  The kernels cover I <= 256 and Bs <= 8; every other valid shape returns I3D_NOT_TAKEN
+ *   (i3d_smp_triplets_takes answers the same without pointers) and the caller composes the step.
+ * i3d_smp_triplets_fwd: one launch, one wave per ji edge; an edge without triplets gets an exact zero row.
+ * i3d_smp_triplets_bwd (E, T >= 1): from g = dL/dout [E, I]: ds8, dt8 [T, Bs] (wave per ji edge), dx [E, I] gathered over the kj-grouped
+ *   list (kj_ptr [E + 1], kj_order [T]: the triplets sorted stably by idx_kj), dw1, dw2 [I, Bs] summed in fp64 over chunks of
+ *   i3d_smp_triplets_chunk() triplets, then per element over the chunks (four quarters, each in chunk order, then the four in order).
+ *   Scratch: partials of i3d_smp_triplets_bwd_partial_floats(T, I, Bs) floats, 8-byte aligned.  Four launches; fixed summation order, no
+ *   atomics, no [T, I] buffer in either direction. */
+int i3d_smp_max_neighbors(void);
+int i3d_smp_radius_count(const float* pos, const int* mol, const int* graph_ptr, int num_nodes, int num_graphs, float cutoff, int* deg,
+                         void* stream);
+int i3d_smp_radius_fill(const float* pos, const int* mol, const int* graph_ptr, const int* in_ptr, int num_nodes, int num_graphs,
+                        int num_edges, float cutoff, int* src, int* dst, float* dist, void* stream);
+int i3d_smp_triplet_count(const int* src, const int* dst, const int* in_ptr, int num_edges, int* count, void* stream);
+int i3d_smp_triplet_fill(const int* src, const int* dst, const int* in_ptr, const int* trip_ptr, int num_edges, int num_triplets,
+                         int* idx_kj, int* idx_ji, void* stream);
+int i3d_smp_bases(const float* pos, const float* dist, const int* src, const int* dst, const int* in_ptr, const int* idx_kj,
+                  const int* idx_ji, int num_edges, int num_triplets, int num_spherical, int num_radial, float cutoff,
+                  const double* zeros, const double* norm, const double* pref, double* rbf_ws, double* cbf_ws, float* angle,
+                  float* torsion, float* sbf, float* t, void* stream);
+int i3d_smp_triplets_takes(int int_emb, int basis_emb);
+int i3d_smp_triplets_chunk(void);
+long i3d_smp_triplets_bwd_partial_floats(int num_triplets, int int_emb, int basis_emb);
+int i3d_smp_triplets_fwd(const float* x, const float* s8, const float* t8, const float* w1, const float* w2, const int* trip_ptr,
+                         const int* idx_kj, int num_edges, int num_triplets, int int_emb, int basis_emb, float* out, void* stream);
+int i3d_smp_triplets_bwd(const float* g, const float* x, const float* s8, const float* t8, const float* w1, const float* w2,
+                         const int* trip_ptr, const int* idx_kj, const int* idx_ji, const int* kj_ptr, const int* kj_order,
+                         int num_edges, int num_triplets, int int_emb, int basis_emb, float* partials, float* dx, float* ds8,
+                         float* dt8, float* dw1, float* dw2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
