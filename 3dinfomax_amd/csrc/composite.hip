@@ -7,6 +7,7 @@
 // edge gather-combine, degree-grouped concat).  Training mode with local batch statistics only; eval mode,
 // synchronised BN and BN-less layers keep using the per-kernel entry points.
 #include "common.h"
+#include "bump.h"
 
 using namespace i3d;
 
@@ -579,6 +580,137 @@ extern "C" long i3d_pna_layer_stats_floats(int num_nodes, int num_edges, int m_p
     tiles = std::max<long>(tiles, 2L * cdiv(num_edges, 64));       // (the row-panel product's 32-row tiles)
     tiles = std::max<long>(tiles, m_padded / 64 + 1);
     return tiles * 3 * f;
+}
+
+// ---- where a layer's buffers live (include/infomax3d_hip.h: i3d_pna_layer_place_fwd / _bwd) --------------------------
+// The one list of the saved and scratch buffers of a layer, their sizes and the chaining of its blocks, for every sequencer
+// (model.hip, layer_native.py): a buffer added to the layer is added here and nowhere else.
+static int check_layer_description(const I3dPnaLayerArgs* a, bool placing) {
+    I3D_CHECK_ARG(a != nullptr && a->n_pre_extra >= 0 && a->n_pre_extra <= I3D_MAX_EXTRA_FC && a->n_post_extra >= 0 &&
+                      a->n_post_extra <= I3D_MAX_EXTRA_FC, "0..3 extra blocks");
+    const I3dEdgeFcArgs& e = a->edge;
+    const I3dGroupedFcArgs& p = a->post;
+    I3D_CHECK_ARG(e.num_nodes > 0 && e.num_edges > 0 && e.f_h > 0 && e.f_out > 0 && e.f_q >= 0 && (e.q == nullptr || e.f_q > 0),
+                  "edge block sizes");
+    I3D_CHECK_ARG(!placing || e.f_q == 0 || e.q != nullptr, "f_q > 0 without a q");
+    I3D_CHECK_ARG(e.q_rows == 0 || (e.f_q > 0 && e.q_rows > 0 && e.v_pad >= e.q_rows), "a table needs q and v_pad >= q_rows");
+    I3D_CHECK_ARG(!a->fused_bn || a->n_post_extra == 0, "fused_bn: one posttrans block");
+    I3D_CHECK_ARG(!a->merge_h || a->fused_bn, "merge_h needs fused_bn");
+    int f = e.f_out;
+    for (int i = 0; i < a->n_pre_extra; ++i) {
+        I3D_CHECK_ARG(a->pre[i].rows == e.num_edges && a->pre[i].f_in == f && a->pre[i].f_out > 0, "pretrans blocks do not chain");
+        f = a->pre[i].f_out;
+    }
+    I3D_CHECK_ARG(a->n_aggregators > 0 && p.agg_width == a->n_aggregators * f, "agg_width is not n_aggregators x message width");
+    I3D_CHECK_ARG(p.num_nodes == e.num_nodes && p.f_out > 0 && p.n_groups > 0, "posttrans block sizes");
+    f = p.f_out;
+    for (int i = 0; i < a->n_post_extra; ++i) {
+        I3D_CHECK_ARG(a->postx[i].rows == e.num_nodes && a->postx[i].f_in == f && a->postx[i].f_out > 0, "posttrans blocks do not chain");
+        f = a->postx[i].f_out;
+    }
+    return I3D_OK;
+}
+
+extern "C" long i3d_pna_layer_place_fwd(I3dPnaLayerArgs* a, float* base) {
+    TRY(check_layer_description(a, base != nullptr));
+    Bump ar(base);
+    I3dEdgeFcArgs& e = a->edge;
+    I3dGroupedFcArgs& p = a->post;
+    const long N = e.num_nodes, E = e.num_edges, Fh = e.f_h, Fo0 = e.f_out, WL = 2 * Fo0 + p.f_out;
+    const bool fused = a->fused_bn != 0, merged = a->merge_h != 0;
+    auto opt = [&](bool exists, long n) { return exists ? ar.take(n) : nullptr; };
+    auto panel = [&](int n, int k) { return opt(merged, i3d_panel_packed_bytes(n, k) / 4); };
+    // what every block keeps: batch statistics, the activation's output, the Linear's where the activation's derivative needs it
+    auto stats = [&](I3dBnTail& t, long f) { t.mean = ar.take(f); t.invstd = ar.take(f); };
+    auto keep = [&](const I3dBnTail& t, long n) { return opt(!simple_act(t.act), n); };
+    // ---- pretrans block 0: edge gather-combine
+    stats(e.tail, Fo0);
+    e.Q = opt(e.f_q > 0, (e.q_rows > 0 ? e.q_rows : E) * Fo0);       // (f_q, not q: a sizing caller may not have its q yet)
+    e.P = ar.take(N * 2 * Fo0);
+    a->Wcat = opt(merged, WL * Fh);         // the products that read h as one GEMM per direction (I3dPnaLayerArgs.merge_h)
+    a->bcat = opt(merged, WL);
+    a->PL = opt(merged, N * WL);
+    a->Wcat_panel = panel(WL, Fh);          // (csrc/panel.hip; packed where Wcat is)
+    a->Wcat_dgrad_panel = panel(Fh, WL);
+    e.xact = ar.take(E * Fo0);
+    e.pre_keep = keep(e.tail, E * Fo0);
+    // fused: the normalised activation is never written, the consumer applies aff while it loads xact
+    a->aff[0] = opt(fused, 3 * Fo0);
+    e.y = opt(!fused, E * Fo0);
+    const float* x = fused ? e.xact : e.y;
+    // ---- further pretrans blocks
+    for (int i = 0; i < I3D_MAX_EXTRA_FC; ++i) a->aff[i + 1] = nullptr;
+    for (int i = 0; i < a->n_pre_extra; ++i) {
+        I3dFcArgs& c = a->pre[i];
+        stats(c.tail, c.f_out);
+        c.x = x;
+        c.xact = ar.take(E * c.f_out);
+        c.W_dgrad_panel = panel(c.f_in, c.f_out);
+        c.W_fwd_panel = panel(c.f_out, c.f_in);
+        c.pre_keep = keep(c.tail, E * c.f_out);
+        a->aff[i + 1] = opt(fused, 3L * c.f_out);
+        c.y = opt(!fused, E * c.f_out);
+        x = fused ? c.xact : c.y;
+    }
+    a->msg = x;
+    // ---- posttrans: the degree-grouped block, then plain ones; the last block's y is the layer output, the caller's
+    stats(p.tail, p.f_out);
+    p.agg = ar.take(N * p.agg_width);
+    p.WD = ar.take((long)p.n_groups * p.f_out * p.agg_width);
+    p.xact = ar.take(N * p.f_out);
+    p.pre_keep = keep(p.tail, N * p.f_out);
+    if (a->n_post_extra > 0) p.y = ar.take(N * p.f_out);
+    x = p.y;
+    for (int i = 0; i < a->n_post_extra; ++i) {
+        I3dFcArgs& c = a->postx[i];
+        stats(c.tail, c.f_out);
+        c.x = x;
+        c.xact = ar.take(N * c.f_out);
+        c.pre_keep = keep(c.tail, N * c.f_out);
+        if (i < a->n_post_extra - 1) c.y = ar.take(N * c.f_out);
+        x = c.y;
+    }
+    return ar.used;
+}
+
+extern "C" int i3d_pna_layer_place_bwd(I3dPnaLayerArgs* a, float* chain, float* side, long* chain_floats, long* side_floats) {
+    I3D_CHECK_ARG(chain_floats != nullptr && side_floats != nullptr, "null count");
+    *chain_floats = *side_floats = 0;
+    const bool place = chain != nullptr && side != nullptr;
+    TRY(check_layer_description(a, place));
+    Bump ch(place ? chain : nullptr), sd(place ? side : nullptr);
+    I3dEdgeFcArgs& e = a->edge;
+    I3dGroupedFcArgs& p = a->post;
+    const long N = e.num_nodes, E = e.num_edges, Fo0 = e.f_out;
+    const bool merged = a->merge_h != 0, table = e.q_rows > 0;
+    // a plain block: the gradient of its Linear output feeds its weight gradients (side), its data gradient the block in front
+    auto fc = [&](I3dFcArgs& c, const float* gy) {
+        c.grad_y = gy;
+        c.grad_pre = sd.take((long)c.rows * c.f_out);
+        c.grad_x = ch.take((long)c.rows * c.f_in);
+        return (const float*)c.grad_x;
+    };
+    const float* gy = a->grad_out;
+    for (int i = a->n_post_extra - 1; i >= 0; --i) gy = fc(a->postx[i], gy);
+    p.grad_y = gy;
+    p.grad_pre = sd.take(N * p.f_out);
+    p.grad_WD = sd.take((long)p.n_groups * p.f_out * p.agg_width);
+    p.grad_agg = ch.take(N * p.agg_width);
+    a->grad_msg = ch.take(E * (p.agg_width / a->n_aggregators));
+    gy = a->grad_msg;
+    for (int i = a->n_pre_extra - 1; i >= 0; --i) gy = fc(a->pre[i], gy);
+    e.grad_y = gy;
+    e.grad_pre = sd.take(E * Fo0);
+    e.grad_P = sd.take(N * 2 * Fo0);
+    a->DL = merged ? sd.take(N * (2 * Fo0 + p.f_out)) : nullptr;        // [dP | dlin] of the merged h-products
+    e.grad_h = ch.take(N * e.f_h);
+    e.grad_Q = table ? sd.take((long)e.v_pad * Fo0) : nullptr;
+    // the edge block's BatchNorm backward fused with its segmented sums (bn.hip: i3d_bn_bwd_edge_sums): partials of the bias
+    // gradient's column sum, taken on the weight-gradient stream
+    a->edge_bias_partial = merged ? sd.take(i3d_bn_bias_partial_floats((int)Fo0)) : nullptr;
+    *chain_floats = ch.used;
+    *side_floats = sd.used;
+    return I3D_OK;
 }
 
 extern "C" int i3d_pna_layer_fwd(const I3dPnaLayerArgs* a, void* stream) {

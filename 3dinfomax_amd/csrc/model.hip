@@ -12,7 +12,7 @@
 // Reference call chain replaced: PNA.forward -> PNAGNN.forward -> [PNALayer.forward]* -> readout -> MLP head
 // (models/pna.py:131-135, 161-166, 199-213, 127-129) and its autograd backward.
 #include "common.h"
-
+#include "bump.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,19 +30,6 @@ using namespace i3d;
     } while (0)
 
 namespace {
-
-inline long al4(long n) { return (n + 3) & ~3L; }
-
-struct Bump {           // bump allocator over a caller-provided float buffer; base == null: sizing pass
-    float* base;
-    long used = 0;
-    explicit Bump(float* b) : base(b) {}
-    float* take(long n) {
-        float* p = base ? base + used : nullptr;
-        used += al4(n);
-        return p;
-    }
-};
 
 struct HeadSaved {
     float* xact = nullptr;
@@ -69,8 +56,22 @@ struct PnaCtx {
     float* hot_atoms = nullptr;     // [N, va] / [n_comb, vb] multi-hot matrices of the encoders' weight gradients (functions of
     float* hot_bonds = nullptr;     // the batch's categorical features only: built on the side stream during the forward pass)
     bool hot_ready = false;
-    int gh_cur = 0;                 // which of the two dL/dh buffers holds the gradient after the layers done so far (backward)
+    // backward scratch (plan_backward)
+    float* gh_top = nullptr;        // [N, F] dL/dh_L, written by the readout's backward
+    float* gh_bottom = nullptr;     // [N, F] dL/dh_0, left by layer 0
+    float* grad_table = nullptr;    // [V, F] dL/d(bond table), summed over the layers
+    float* head_colsum_ws = nullptr;
+    float* enc_hot_atoms = nullptr; // the multi-hot matrices when the forward pass has not built them, and the atom tables'
+    float* enc_hot_bonds = nullptr; // gradient over the vocabulary rounded up to 4
+    float* enc_atoms_out = nullptr;
 };
+
+int vocabulary(const int* dims, int n) {      // rows of the concatenated embedding tables
+    int v = 0;
+    for (int k = 0; k < n; ++k) v += dims[k];
+    return v;
+}
+inline int up32(int v) { return (v + 31) / 32 * 32; }
 
 // the [rows, v] multi-hot matrices of the atom / bond-combination features (columns: the concatenated vocabularies, padded
 // to 32): embedding-table gradients are their transposes times dL/d(embedding)
@@ -97,7 +98,7 @@ bool msg_bf16_storage(const I3dPnaModel& m, long E) {
 
 bool simple_act(int act) { return act == I3D_ACT_NONE || act == I3D_ACT_RELU || act == I3D_ACT_LEAKY_RELU; }
 
-void fill_tail(I3dBnTail& t, const I3dFcParams& p, float* mean, float* invstd) {
+void fill_tail(I3dBnTail& t, const I3dFcParams& p, float* mean = nullptr, float* invstd = nullptr) {
     t.act = p.act;
     t.post_act = I3D_ACT_NONE;
     t.eps = p.eps;
@@ -134,30 +135,6 @@ int wgrad(int M, int N, int K, const float* A, int lda, const float* B, int ldb,
           void* stream) {
     if (K >= 1024) return i3d_gemm_f32_ws(1, 0, M, N, K, A, lda, B, ldb, C, ldc, nullptr, 0, ws, ws_bytes, stream);
     return i3d_gemm_f32(1, 0, M, N, K, A, lda, B, ldb, C, ldc, nullptr, 0, stream);
-}
-
-// the head's backward buffers (read by its weight gradients on the side stream: kept apart from the layers' shared region),
-// and a column-reduction scratch of that stream's own
-long head_floats(const I3dPnaModel& m, long B) {
-    long t = 0;
-    for (int i = 0; i < m.n_head; ++i) t += al4(B * (long)m.head[i].f_in) + 2 * al4(B * (long)m.head[i].f_out);
-    return t;
-}
-long head_colsum_floats(const I3dPnaModel& m, long B) {
-    long t = 0;
-    for (int i = 0; i < m.n_head; ++i) t = std::max(t, (i3d_colreduce_workspace_bytes((int)B, m.head[i].f_out) + 3) / 4);
-    return al4(t);
-}
-
-// floats of the buffers of layer l's backward pass that the weight-gradient stream reads or writes
-long side_floats(const I3dPnaModel& m, const I3dPnaBatch& b, int l) {
-    const long N = b.num_nodes, E = b.num_edges, F = m.hidden;
-    const long f_msg = m.pre[l][m.n_pre - 1].f_out, A = m.n_aggregators * f_msg, Fo0 = m.pre[l][0].f_out;
-    long t = al4(N * F) + al4((long)b.n_groups * F * A);
-    for (int i = 1; i < m.n_pre; ++i) t += al4(E * (long)m.pre[l][i].f_out);
-    t += al4(E * Fo0) + al4(N * 2 * Fo0) + al4((long)b.v_pad * Fo0) + al4(i3d_bn_bias_partial_floats((int)Fo0));      // (edge_bias_partial)
-    t += al4(N * (2 * Fo0 + F));        // DL (merged h-products)
-    return t;
 }
 
 int check_model(const I3dPnaModel* m, const I3dPnaBatch* b) {
@@ -211,63 +188,46 @@ long plan_forward(PnaCtx& c, float* saved, float* node_emb, float* out) {
         a.merge_h = 1;      // the products that read h as ONE GEMM per direction (Wcat / PL below, DL in the backward pass)
         a.stats_ws = stats_ws;
         c.h[l + 1] = (l == L - 1) ? node_emb : ar.take((long)N * F);
-        // ---- pretrans block 0: edge gather-combine
+        // ---- describe the layer: sizes, parameters, inputs, flags ...
         I3dEdgeFcArgs& e = a.edge;
         const I3dFcParams& p0 = m.pre[l][0];
-        const int Fo0 = p0.f_out;
-        fill_tail(e.tail, p0, ar.take(Fo0), ar.take(Fo0));
-        e.num_nodes = N; e.num_edges = E; e.f_h = F; e.f_q = F; e.f_out = Fo0; e.ldw = p0.f_in;
+        fill_tail(e.tail, p0);
+        e.num_nodes = N; e.num_edges = E; e.f_h = F; e.f_q = F; e.f_out = p0.f_out; e.ldw = p0.f_in;
         e.q_rows = b.n_comb; e.v_pad = b.v_pad; e.q_code = c.codes; e.onehot = c.onehot;
         e.h = c.h[l]; e.q = c.bond_table; e.W = p0.W; e.bias = p0.bias;
         e.src_s = b.src_s; e.dst_s = b.dst_s; e.in_ptr = b.in_ptr; e.out_ptr = b.out_ptr; e.out_epos = b.out_epos;
-        e.Q = ar.take((long)b.n_comb * Fo0);
-        e.P = ar.take((long)N * 2 * Fo0);
-        a.Wcat = ar.take((long)(2 * Fo0 + F) * F);
-        a.bcat = ar.take(2 * Fo0 + F);
-        a.PL = ar.take((long)N * (2 * Fo0 + F));
-        a.Wcat_panel = ar.take(i3d_panel_packed_bytes(2 * Fo0 + F, F) / 4);      // (csrc/panel.hip; packed where Wcat is)
-        a.Wcat_dgrad_panel = ar.take(i3d_panel_packed_bytes(F, 2 * Fo0 + F) / 4);
-        e.xact = ar.take((long)E * Fo0);
-        a.aff[0] = ar.take(3L * Fo0);
-        const float* x = e.xact;
-        int f_in = Fo0;
+        int f_in = p0.f_out;
         a.n_pre_extra = m.n_pre - 1;
         for (int i = 1; i < m.n_pre; ++i) {
             const I3dFcParams& p = m.pre[l][i];
             I3dFcArgs& fc = a.pre[i - 1];
-            fill_tail(fc.tail, p, ar.take(p.f_out), ar.take(p.f_out));
+            fill_tail(fc.tail, p);
             fc.rows = E; fc.f_in = f_in; fc.f_out = p.f_out; fc.ldw = p.f_in;
-            fc.x = x; fc.W = p.W; fc.bias = p.bias;
-            fc.xact = ar.take((long)E * p.f_out);
-            fc.W_dgrad_panel = ar.take(i3d_panel_packed_bytes(f_in, p.f_out) / 4);
-            fc.W_fwd_panel = ar.take(i3d_panel_packed_bytes(p.f_out, f_in) / 4);
-            a.aff[i] = ar.take(3L * p.f_out);
-            x = fc.xact;
+            fc.W = p.W; fc.bias = p.bias;
             f_in = p.f_out;
         }
-        // ---- aggregation (identity block only: the scalers live in the per-degree weights)
+        // aggregation (identity block only: the scalers live in the per-degree weights)
         a.n_aggregators = m.n_aggregators;
         for (int i = 0; i < m.n_aggregators; ++i) a.aggregators[i] = m.aggregators[i];
         a.n_scalers = 1; a.scalers[0] = I3D_SCALE_IDENTITY; a.force_scalers = 0; a.avg_d_log = m.avg_d_log;
-        a.msg = x;
-        const int A = m.n_aggregators * f_in;
-        // ---- posttrans: degree-grouped block
+        // posttrans: degree-grouped block
         I3dGroupedFcArgs& g = a.post;
         const I3dFcParams& pp = m.post[l];
-        fill_tail(g.tail, pp, ar.take(F), ar.take(F));
-        g.num_nodes = N; g.f_h = F; g.f_out = F; g.agg_width = A; g.ldw = pp.f_in;
+        fill_tail(g.tail, pp);
+        g.num_nodes = N; g.f_h = F; g.f_out = F; g.agg_width = m.n_aggregators * f_in; g.ldw = pp.f_in;
         g.n_groups = b.n_groups; g.n_scalers = m.n_scalers; g.m_padded = b.m_padded;
         for (int k = 0; k < b.n_groups; ++k) { g.group_start[k] = b.group_start[k]; g.group_count[k] = b.group_count[k]; }
         for (int k = 0; k < b.n_groups * m.n_scalers; ++k) g.coef[k] = c.coef[k];
         g.h = c.h[l]; g.W = pp.W; g.bias = pp.bias;
-        g.agg = ar.take((long)N * A);
         g.deg_rows = b.deg_rows; g.deg_tile_group = b.deg_tile_group;
-        g.WD = ar.take((long)b.n_groups * F * A);
-        g.xact = ar.take((long)N * F);
         g.y = c.h[l + 1];
         a.n_post_extra = 0;
         a.residual = m.residual ? 1 : 0;
         g.residual = m.residual ? c.h[l] : nullptr;
+        // ---- ... and place its buffers
+        const long used = i3d_pna_layer_place_fwd(&a, ar.here());
+        if (used < 0) return used;
+        ar.take(used);
     }
     // ---- readout + head
     c.readout = ar.take((long)B * m.n_readout * F);
@@ -296,15 +256,63 @@ long plan_forward(PnaCtx& c, float* saved, float* node_emb, float* out) {
         x = y;
     }
     c.out = out;
-    {
-        long oa = 0, ob = 0;
-        for (int k = 0; k < m.n_atom_tables; ++k) oa += m.atom_dims[k];
-        for (int k = 0; k < m.n_bond_tables; ++k) ob += m.bond_dims[k];
-        c.hot_atoms = ar.take((long)N * ((oa + 31) / 32 * 32));
-        c.hot_bonds = ar.take((long)b.n_comb * ((ob + 31) / 32 * 32));
-    }
+    c.hot_atoms = ar.take((long)N * up32(vocabulary(m.atom_dims, m.n_atom_tables)));
+    c.hot_bonds = ar.take((long)b.n_comb * up32(vocabulary(m.bond_dims, m.n_bond_tables)));
     c.saved_floats = ar.used;
     return ar.used;
+}
+
+// The backward scratch of a forward-planned ctx, laid out in `scratch` (null: sizing); every part of a pass sees the same
+// addresses.  In order: the state between the layers (dL/dh ping-pong, the bond table's gradient); what the weight-gradient
+// stream reads or writes - one set per layer and the head's, alive for the whole pass: that stream is the critical path of a
+// layer and is joined once, at the end of the model's backward pass (a join per layer made the chain of the NEXT layer wait
+// for it); the region the layers' chains reuse one after the other, and the encoders at the end.
+long plan_backward(PnaCtx& c, float* scratch) {
+    const I3dPnaModel& m = c.m;
+    const I3dPnaBatch& b = c.b;
+    const int N = b.num_nodes, B = b.num_graphs, F = m.hidden, L = m.n_layers;
+    Bump top(scratch);
+    float* gh[2] = {top.take((long)N * F), top.take((long)N * F)};
+    c.grad_table = top.take((long)b.n_comb * F);
+    std::vector<float*> side(L, nullptr);
+    long chain_floats = 0, n_chain = 0, n_side = 0;
+    int cur = L & 1;
+    c.gh_top = gh[cur];
+    for (int l = L - 1; l >= 0; --l) {
+        I3dPnaLayerArgs& a = c.layers[l];
+        // a residual layer accumulates dL/dh_in on top of the incoming gradient IN PLACE (dh_in = dh_out + ...: the separate
+        // add pass over [N, F] is gone, composite.hip: i3d_pna_layer_bwd); others ping-pong between the two buffers
+        const int nxt = a.residual ? cur : cur ^ 1;
+        a.grad_out = gh[cur];
+        a.post.grad_h = gh[nxt];
+        a.edge.grad_q = c.grad_table;
+        a.edge.grad_q_accumulate = (l == L - 1) ? 0 : 1;        // the bond table feeds every layer: its gradient is their sum
+        cur = nxt;
+        if (i3d_pna_layer_place_bwd(&a, nullptr, nullptr, &n_chain, &n_side) != I3D_OK) return -1;
+        side[l] = top.take(n_side);
+        chain_floats = std::max(chain_floats, n_chain);
+    }
+    c.gh_bottom = gh[cur];
+    // the head's chain: its weight and bias gradients - leaves on the weight-gradient stream - read grad_pre and x
+    long colsum_bytes = 0;
+    for (int i = m.n_head - 1; i >= 0; --i) {
+        I3dFcArgs& fc = c.head_args[i];
+        const I3dFcParams& p = m.head[i];
+        fc.grad_x = top.take((long)B * p.f_in);
+        // gradient of the Linear's output: the BatchNorm backward's result, else the activation's (grad_y itself without one)
+        fc.grad_pre = (p.gamma != nullptr || p.act != I3D_ACT_NONE) ? top.take((long)B * p.f_out) : nullptr;
+        colsum_bytes = std::max(colsum_bytes, i3d_colreduce_workspace_bytes(B, p.f_out));
+    }
+    c.head_colsum_ws = top.take((colsum_bytes + 3) / 4);      // a column-reduction scratch of that stream's own
+    float* const rest = top.here();
+    for (int l = 0; l < L; ++l)       // (every description was accepted by the sizing call above)
+        (void)i3d_pna_layer_place_bwd(&c.layers[l], rest, side[l], &n_chain, &n_side);
+    Bump enc(rest);
+    const int oa = vocabulary(m.atom_dims, m.n_atom_tables), ob = vocabulary(m.bond_dims, m.n_bond_tables);
+    c.enc_hot_atoms = enc.take((long)N * up32(oa));
+    c.enc_hot_bonds = enc.take((long)b.n_comb * up32(ob));
+    c.enc_atoms_out = enc.take((long)((oa + 3) / 4 * 4) * F);
+    return top.used + std::max(chain_floats, enc.used);
 }
 
 }  // namespace
@@ -319,27 +327,11 @@ extern "C" long i3d_pna_model_saved_floats(const I3dPnaModel* m, const I3dPnaBat
 
 extern "C" long i3d_pna_model_scratch_floats(const I3dPnaModel* m, const I3dPnaBatch* b) {
     if (check_model(m, b) != I3D_OK) return -1;
-    // an upper bound of the takes of i3d_pna_model_bwd: `layer` counts the side stream's buffers of a layer a second time
-    const long N = b->num_nodes, E = b->num_edges, B = b->num_graphs, F = m->hidden;
-    const long top = 2 * al4(N * F) + al4((long)b->n_comb * F);
-    const long head = head_floats(*m, B) + head_colsum_floats(*m, B);
-    long layer = 0;
-    for (int l = 0; l < m->n_layers; ++l) {
-        const long f_msg = m->pre[l][m->n_pre - 1].f_out, A = m->n_aggregators * f_msg, Fo0 = m->pre[l][0].f_out;
-        long t = al4(N * F) + al4((long)b->n_groups * F * A) + al4(N * A) + al4(E * f_msg);
-        for (int i = 1; i < m->n_pre; ++i)
-            t += al4(E * (long)m->pre[l][i].f_out) + al4(E * (long)m->pre[l][i].f_in);
-        t += al4(E * Fo0) + al4(N * 2 * Fo0) + al4(N * F) + al4((long)b->v_pad * Fo0) + al4(i3d_bn_bias_partial_floats(Fo0));
-        t += al4(N * (2 * Fo0 + F));
-        layer = std::max(layer, t);
-    }
-    long oa = 0, ob = 0;
-    for (int k = 0; k < m->n_atom_tables; ++k) oa += m->atom_dims[k];
-    for (int k = 0; k < m->n_bond_tables; ++k) ob += m->bond_dims[k];
-    const long emb = al4(N * ((oa + 31) / 32 * 32)) + al4((long)b->n_comb * ((ob + 31) / 32 * 32)) + al4(((oa + 3) / 4 * 4) * F);
-    long side = 0;
-    for (int l = 0; l < m->n_layers; ++l) side += side_floats(*m, *b, l);
-    return top + side + head + std::max(layer, emb);
+    PnaCtx c;
+    c.m = *m;
+    c.b = *b;
+    if (plan_forward(c, nullptr, nullptr, nullptr) < 0) return -1;
+    return plan_backward(c, nullptr);
 }
 
 extern "C" int i3d_pna_model_fwd(const I3dPnaModel* m, const I3dPnaBatch* b, float* saved, float* node_emb, float* edge_emb,
@@ -351,7 +343,10 @@ extern "C" int i3d_pna_model_fwd(const I3dPnaModel* m, const I3dPnaBatch* b, flo
     I3D_CHECK_ARG(c != nullptr, "out of host memory");
     c->m = *m;
     c->b = *b;
-    plan_forward(*c, saved, node_emb, out);
+    if (plan_forward(*c, saved, node_emb, out) < 0) {
+        delete c;
+        return I3D_ERR_INVALID;
+    }
     *ctx_out = c;
     const int N = b->num_nodes, E = b->num_edges, B = b->num_graphs, F = m->hidden, L = m->n_layers;
     // ---- encoders (reference commons/mol_encoder.py:34-42, 65-73; models/pna.py:162-163)
@@ -454,27 +449,18 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
     I3D_CHECK_ARG(m.grad_atom_tables != nullptr && m.grad_bond_tables != nullptr && m.post[0].grad_W != nullptr,
                   "gradient buffers not set");
     const I3dPnaBatch& b = c->b;
-    const int N = b.num_nodes, E = b.num_edges, B = b.num_graphs, F = m.hidden, L = m.n_layers;
+    const int N = b.num_nodes, B = b.num_graphs, F = m.hidden, L = m.n_layers;
     I3D_CHECK_ARG(part >= 0 && part <= 2 && (part == 0 || (split > 0 && split < L)), "bad part / split");
     const int l_hi = part == 2 ? split : L, l_lo = part == 1 ? split : 0;      // layers [l_lo, l_hi) in this call
-    Bump top(scratch);
-    float* gh[2] = {top.take((long)N * F), top.take((long)N * F)};      // dL/dh, ping-pong between layers
-    float* grad_table = top.take((long)b.n_comb * F);                  // dL/d(bond table), summed over the layers
-    // buffers the weight-gradient stream reads or writes: one set per layer, that stream is joined once, at the end of the model's
-    // backward pass (it is the critical path of a layer: a join per layer made the chain of the NEXT layer wait for it)
+    if (plan_backward(*c, scratch) < 0) return I3D_ERR_INVALID;      // (every part of a pass: the same addresses)
     // the last 16 MB of the weight-gradient scratch belong to the launches the MAIN stream issues while the side stream is
     // busy (the atom tables' gradient at the end); the side stream's launches see the front part only
     const long tail_bytes = (gemm_workspace != nullptr && gemm_workspace_bytes >= (64L << 20)) ? (16L << 20) : 0;
     char* const tail_ws = tail_bytes > 0 ? (char*)gemm_workspace + (gemm_workspace_bytes - tail_bytes) / 256 * 256 : nullptr;
     const long side_ws_bytes = tail_bytes > 0 ? (long)(tail_ws - (char*)gemm_workspace) : gemm_workspace_bytes;
-    std::vector<float*> side(L, nullptr);
-    for (int l = 0; l < L; ++l) side[l] = top.take(side_floats(m, b, l));
-    float* const head_buf = top.take(head_floats(m, B));
-    float* const head_colsum_ws = top.take(head_colsum_floats(m, B));
-    float* const rest = scratch + top.used;
     // the head's weight / bias gradients (leaves); only invoked inside this call: a plain lambda over the locals (a
     // std::function with by-value captures copied the whole model description and heap-allocated per backward call)
-    const float* gpre_of[I3D_MAX_HEAD_FC] = {};
+    const float* gpre_of[I3D_MAX_HEAD_FC] = {};      // gradient of each BatchNorm-less block's Linear output
     auto head_leaves = [&](void* wst) -> int {
         for (int i = m.n_head - 1; i >= 0; --i) {
             I3dFcArgs& fc = c->head_args[i];
@@ -485,7 +471,7 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
                 TRY(wgrad(p.f_out, p.f_in, B, gpre_of[i], p.f_out, fc.x, p.f_in, p.grad_W, p.f_in, gemm_workspace, side_ws_bytes, wst));
                 void* cws = bn_workspace;
                 if (wst != stream) {      // a reduction scratch of the side stream's own; its arrival counters (the first bytes) start at 0
-                    cws = head_colsum_ws;
+                    cws = c->head_colsum_ws;
                     if (hipMemsetAsync(cws, 0, 256, (hipStream_t)wst) != hipSuccess) {
                         i3d::set_error("i3d_pna_model_bwd: clearing the head's reduction scratch failed");
                         return I3D_ERR_LAUNCH;
@@ -499,31 +485,28 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
     bool leaves_pending = false;
     // ---- head, last block first: the chain (BatchNorm backward, data gradients) on the caller's stream, then ONE fork and the
     // head's weight and bias gradients - leaves - on the weight-gradient stream, next to the readout's and the last layer's
-    // chain (round 2 ran them in line: three launches of latency on the critical path).  Their inputs live in `head_buf`,
-    // outside the region the layers reuse.
+    // chain (round 2 ran them in line: three launches of latency on the critical path).  Their inputs live outside the
+    // region the layers reuse (plan_backward).
     if (part != 2) {
-        Bump ar(head_buf);
         const float* gy = grad_out;
         for (int i = m.n_head - 1; i >= 0; --i) {
             I3dFcArgs& fc = c->head_args[i];
             const I3dFcParams& p = m.head[i];
-            float* gx = ar.take((long)B * p.f_in);
+            fc.grad_y = gy;
             if (p.gamma != nullptr) {
                 set_ws(fc.tail, bn_workspace, gemm_workspace, side_ws_bytes);
-                fc.grad_y = gy; fc.grad_pre = ar.take((long)B * p.f_out); fc.grad_x = gx;
                 fc.grad_W = p.grad_W; fc.grad_bias = p.grad_bias; fc.grad_gamma = p.grad_gamma; fc.grad_beta = p.grad_beta;
                 TRY(i3d_fc_bn_bwd_chain(&fc, stream));
             } else {
                 const float* gpre = gy;
                 if (p.act != I3D_ACT_NONE) {
-                    float* t = ar.take((long)B * p.f_out);
-                    TRY(i3d_act_bwd(gy, fc.xact, (long)B * p.f_out, p.act, t, stream));
-                    gpre = t;
+                    TRY(i3d_act_bwd(gy, fc.xact, (long)B * p.f_out, p.act, fc.grad_pre, stream));
+                    gpre = fc.grad_pre;
                 }
-                TRY(i3d_gemm_f32(0, 0, B, p.f_in, p.f_out, gpre, p.f_out, p.W, p.f_in, gx, p.f_in, nullptr, 0, stream));
+                TRY(i3d_gemm_f32(0, 0, B, p.f_in, p.f_out, gpre, p.f_out, p.W, p.f_in, fc.grad_x, p.f_in, nullptr, 0, stream));
                 gpre_of[i] = gpre;
             }
-            gy = gx;
+            gy = fc.grad_x;
         }
         constexpr bool leaves_aside = true;
         // the leaves go to the weight-gradient stream behind the fork the LAST layer's backward makes anyway (a fork of their own
@@ -531,62 +514,32 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         leaves_pending = leaves_aside && l_hi == L && l_hi > l_lo;
         if (!leaves_pending) TRY(head_leaves(stream));
         // readout backward -> dL/dh_L
-        TRY(i3d_segment_readout_bwd(gy, c->h[L], b.graph_ptr, B, F, m.readout_ops, m.n_readout, gh[L & 1], stream));
-        c->gh_cur = L & 1;
+        TRY(i3d_segment_readout_bwd(gy, c->h[L], b.graph_ptr, B, F, m.readout_ops, m.n_readout, c->gh_top, stream));
     }
-    // ---- layers, last first
+    // ---- layers, last first (buffers, chaining and the dL/dh ping-pong: plan_backward)
     for (int l = l_hi - 1; l >= l_lo; --l) {
         I3dPnaLayerArgs& a = c->layers[l];
-        Bump ar(rest);
-        Bump sd(side[l]);       // the side stream's buffers of this layer
         a.defer_join = 1;
         // The first layer's weight gradients (the last ones of a backward pass, and what the step waits for at its very end) as two
         // launches, the posttrans products early, next to that layer's chain: only the pretrans / bond-table products are left when
         // the chain ends (2.141 against 2.152 ms, tools/ab.sh, 5 interleaved runs; every layer split that way loses 40 us: one more
         // launch + reduction per layer for work that was hidden anyway)
         a.wgrad_split = l == 0 ? 1 : 0;
-        // a residual layer accumulates dL/dh_in on top of the incoming gradient IN PLACE (dh_in = dh_out + ...: the separate
-        // add pass over [N, F] is gone, composite.hip: i3d_pna_layer_bwd); others ping-pong between the two buffers
-        const int cur = c->gh_cur, nxt = a.residual ? cur : cur ^ 1;
-        const float* grad_in = gh[cur];
-        a.grad_out = grad_in;
         I3dGroupedFcArgs& g = a.post;
         const I3dFcParams& pp = m.post[l];
         set_ws(g.tail, bn_workspace, gemm_workspace, side_ws_bytes);
         g.grad_W = pp.grad_W; g.grad_bias = pp.grad_bias; g.grad_gamma = pp.grad_gamma; g.grad_beta = pp.grad_beta;
-        g.grad_y = grad_in;
-        g.grad_pre = sd.take((long)N * F);
-        g.grad_WD = sd.take((long)b.n_groups * F * g.agg_width);
-        g.grad_h = gh[nxt];
-        g.grad_agg = ar.take((long)N * g.agg_width);
-        const int f_msg = a.n_pre_extra > 0 ? a.pre[a.n_pre_extra - 1].f_out : a.edge.f_out;
-        a.grad_msg = ar.take((long)E * f_msg);
-        const float* gy = a.grad_msg;
         for (int i = a.n_pre_extra - 1; i >= 0; --i) {
             I3dFcArgs& fc = a.pre[i];
             const I3dFcParams& p = m.pre[l][i + 1];
             set_ws(fc.tail, bn_workspace, gemm_workspace, side_ws_bytes);
             fc.grad_W = p.grad_W; fc.grad_bias = p.grad_bias; fc.grad_gamma = p.grad_gamma; fc.grad_beta = p.grad_beta;
-            fc.grad_y = gy;
-            fc.grad_pre = sd.take((long)E * fc.f_out);
-            fc.grad_x = ar.take((long)E * fc.f_in);
-            gy = fc.grad_x;
         }
         I3dEdgeFcArgs& e = a.edge;
         const I3dFcParams& p0 = m.pre[l][0];
         set_ws(e.tail, bn_workspace, gemm_workspace, side_ws_bytes);
         e.grad_W = p0.grad_W; e.grad_bias = p0.grad_bias; e.grad_gamma = p0.grad_gamma; e.grad_beta = p0.grad_beta;
-        e.grad_y = gy;
-        e.grad_pre = sd.take((long)E * e.f_out);
-        e.grad_P = sd.take((long)N * 2 * e.f_out);
-        a.DL = sd.take((long)N * (2 * e.f_out + F));
-        e.grad_h = ar.take((long)N * F);
-        e.grad_Q = sd.take((long)b.v_pad * e.f_out);
-        a.edge_bias_partial = sd.take(i3d_bn_bias_partial_floats(e.f_out));
-        e.grad_q = grad_table;
-        e.grad_q_accumulate = (l == L - 1) ? 0 : 1;        // the bond table feeds every layer: its gradient is their sum
         TRY(i3d_pna_layer_bwd(&a, stream));
-        c->gh_cur = nxt;
         if (leaves_pending) {
             void* wst = stream;
             TRY(i3d_wgrad_stream_peek(stream, &wst));
@@ -603,16 +556,13 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
     // gradients (round 2: after it, 30 us at the very end of the step); its split-K slices go through a slice of the scratch
     // of its own (the side stream's launches own the front of it).  The bond tables' needs the side stream's grad_table.
     {
-        Bump ar(rest);
-        int oa = 0, ob = 0;
-        for (int k = 0; k < m.n_atom_tables; ++k) oa += m.atom_dims[k];
-        for (int k = 0; k < m.n_bond_tables; ++k) ob += m.bond_dims[k];
-        const int va = (oa + 31) / 32 * 32, vb = (ob + 31) / 32 * 32;
+        const int oa = vocabulary(m.atom_dims, m.n_atom_tables), ob = vocabulary(m.bond_dims, m.n_bond_tables);
+        const int va = up32(oa), vb = up32(ob);
         float* hot = c->hot_atoms;
         float* hotb = c->hot_bonds;
         if (!c->hot_ready) {            // not built during the forward pass (no side stream): here, into scratch
-            hot = ar.take((long)N * va);
-            hotb = ar.take((long)b.n_comb * vb);
+            hot = c->enc_hot_atoms;
+            hotb = c->enc_hot_bonds;
             TRY(encoder_multihot(*c, hot, hotb, stream));
         }
         const bool own_ws = tail_bytes > 0;
@@ -620,9 +570,9 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         // against 12 us).  The multi-hot matrix has zero columns up to va, so the product is taken over oa rounded up to 4 into
         // scratch and the real rows are copied out (same tiles, same split, same summation order: same bits)
         const int oa4 = (oa + 3) / 4 * 4;
-        float* atoms_out = oa4 == oa ? m.grad_atom_tables : ar.take((long)oa4 * F);
+        float* atoms_out = oa4 == oa ? m.grad_atom_tables : c->enc_atoms_out;
         auto atom_tables = [&](void* ws, long wsb) -> int {
-            TRY(wgrad(oa4, F, N, hot, va, gh[c->gh_cur], F, atoms_out, F, ws, wsb, stream));
+            TRY(wgrad(oa4, F, N, hot, va, c->gh_bottom, F, atoms_out, F, ws, wsb, stream));
             if (atoms_out != m.grad_atom_tables &&
                 hipMemcpyAsync(m.grad_atom_tables, atoms_out, (size_t)oa * F * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
                 i3d::set_error("i3d_pna_model_bwd: copy of the atom-table gradient failed");
@@ -637,11 +587,11 @@ extern "C" int i3d_pna_model_bwd_part(void* ctx, const I3dPnaModel* grads_from, 
         constexpr bool bond_aside = true;
         if (bond_aside && own_ws && c->hot_ready) TRY(i3d_wgrad_stream_peek(stream, &bst));
         if (bst != stream)
-            TRY(wgrad(ob, F, b.n_comb, hotb, vb, grad_table, F, m.grad_bond_tables, F, gemm_workspace, side_ws_bytes, bst));
+            TRY(wgrad(ob, F, b.n_comb, hotb, vb, c->grad_table, F, m.grad_bond_tables, F, gemm_workspace, side_ws_bytes, bst));
         TRY(i3d_wgrad_stream_join(stream));
         if (!own_ws) TRY(atom_tables(gemm_workspace, gemm_workspace_bytes));
         if (bst == stream)
-            TRY(wgrad(ob, F, b.n_comb, hotb, vb, grad_table, F, m.grad_bond_tables, F, gemm_workspace, gemm_workspace_bytes, stream));
+            TRY(wgrad(ob, F, b.n_comb, hotb, vb, c->grad_table, F, m.grad_bond_tables, F, gemm_workspace, gemm_workspace_bytes, stream));
     }
     return I3D_OK;
 }

@@ -862,6 +862,23 @@ int i3d_bn_eval_aff_multi(const I3dBnEvalAff* entries /* host */, int n, void* s
 /* floats of I3dPnaLayerArgs.stats_ws for a layer with these dimensions (f = widest block output) */
 long i3d_pna_layer_stats_floats(int num_nodes, int num_edges, int m_padded, int f);
 
+/* Where the buffers of one PNA layer live: the ONE list of a layer's saved and scratch buffers, for every sequencer.
+ * The caller describes the layer - the sizes of every block and ldw, n_pre_extra / n_post_extra / n_aggregators, each tail's
+ * act / post_act, fused_bn, merge_h, whether there is a q (edge.f_q > 0; a placing call wants edge.q itself then) / q_rows /
+ * v_pad, post.n_groups / agg_width (backward also: grad_out) - and these fill in every saved or scratch pointer and chain
+ * the blocks (pre[0].x = edge.y or, fused, edge.xact; msg; postx[0].x = post.y; backward: each block's grad_y = the grad_x
+ * of the block behind it, the top one = grad_out).  A buffer the
+ * description rules out (pre_keep under none / ReLU / LeakyReLU, y of a fused pretrans block, aff[] of a non-fused one, the
+ * merge_h buffers and panel images without merge_h, Q / grad_Q without q or a table) is set to NULL.  Left to the caller:
+ * h, q, parameters and their gradients, index arrays, stats_ws, the layer output (y of the last posttrans block) and the
+ * residual pointers, grad_out, post.grad_h, edge.grad_q / grad_q_accumulate, workspaces, events, control flags.
+ * Every buffer starts a multiple of 4 floats from its base.  A NULL base: sizing only (the pointers come out NULL).
+ * Forward: returns the floats used behind `base`, < 0 for a description no layer has. */
+long i3d_pna_layer_place_fwd(I3dPnaLayerArgs* args, float* base);
+/* Backward: `chain` takes the buffers only the layer's own stream touches (a sequencer may reuse it layer by layer), `side`
+ * those the weight-gradient stream reads or writes (alive until that stream is joined).  Both counts are always written. */
+int i3d_pna_layer_place_bwd(I3dPnaLayerArgs* args, float* chain, float* side, long* chain_floats, long* side_floats);
+
 /* ---- the edge stage of the 3D network, one lane per edge (net3d_edge.hip) ---------------------------------------
  * reference models/net3d.py:57-81 + 100-118 for propagation_depth 1, one message block, broadcast node embedding:
  *   e0 = post(BN_in(act(W_in fourier(d) + b_in))),  m = BN_msg(act(W_msg [emb | emb | e0] + b_msg)),

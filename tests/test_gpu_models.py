@@ -292,6 +292,54 @@ def test_bond_table_path_matches_dense_bond_embeddings(amd, composite, fused_mod
     grads_close(res[True][3], res[False][3], 1e-4, 'pna ')
 
 
+@pytest.mark.parametrize('case', ['pretrans_2', 'posttrans_2', 'silu'])
+def test_layer_planner_on_more_layer_shapes(amd, case, monkeypatch):
+    """Both sequencers place a layer's buffers through one planner (i3d_pna_layer_place_fwd / _bwd); one forward and backward of a
+    small model on layer shapes the tests above do not reach.  Two pretrans blocks: the whole-model C call against the
+    Python-sequenced layer C calls, the same bits in the output, the node embeddings and every parameter gradient.  Two posttrans
+    blocks, and an activation that keeps the Linear's output (the non-fused layer form: y of every pretrans block, pre_keep, the
+    chain of plain posttrans blocks): the layer C call against the block path, the same bits in the output and the node
+    embeddings.  Their parameter gradients are not the same bits, before the planner either (24 of 50 and 17 of 42 tensors equal:
+    the layer call sums the weight gradients in one launch, the blocks in one per product), and are held to the bound
+    test_bond_table_path_matches_dense_bond_embeddings sets between these two paths."""
+    native = importlib.import_module('3dinfomax_amd.pna_native')
+    layer_native = importlib.import_module('3dinfomax_amd.layer_native')
+    kw = dict(PNA_SMALL, **{'pretrans_2': dict(pretrans_layers=2), 'posttrans_2': dict(posttrans_layers=2),
+                            'silu': dict(activation='silu')}[case])
+    mols = synth.make_dataset(24, seed=17)
+    pna = amd.PNA(avg_d=1.0, device='cuda:0', **kw)
+    _det_load(pna, 'pnaPlan')
+    pna.cuda().train()
+    sd0 = {k: v.clone() for k, v in pna.state_dict().items()}
+    calls = []
+    real_forward, real_eligible = layer_native.forward, layer_native.eligible
+    monkeypatch.setattr(layer_native, 'forward', lambda *a, **k: (calls.append(1), real_forward(*a, **k))[1])
+
+    def run(model_call, layer_call):
+        monkeypatch.setattr(native, 'NATIVE_MODEL', model_call)
+        monkeypatch.setattr(layer_native, 'eligible', real_eligible if layer_call else (lambda *a, **k: False))
+        pna.load_state_dict(sd0)
+        pna.zero_grad(set_to_none=True)
+        g2, _ = make_batch(amd, mols)
+        z = pna(g2)
+        (z * z).sum().backward()
+        return z.detach().clone(), g2.ndata['feat'].detach().clone(), {k: v.clone() for k, v in param_grads(pna).items()}
+    if case == 'pretrans_2':
+        ref = run(True, True)
+        assert calls == [], 'the model C call takes this pass'
+        res = run(False, True)
+    else:
+        res, ref = run(False, True), run(False, False)
+    assert len(calls) == kw['propagation_depth'], 'the layer C call must take every layer of one pass, and of one only'
+    assert torch.equal(res[0], ref[0]) and torch.equal(res[1], ref[1])
+    assert sorted(res[2]) == sorted(ref[2]) and len(res[2]) > 20
+    if case == 'pretrans_2':
+        for k in res[2]:
+            assert torch.equal(res[2][k], ref[2][k]), k
+    else:
+        grads_close({k: v.cpu() for k, v in res[2].items()}, {k: v.cpu() for k, v in ref[2].items()}, 1e-4, 'pna ')
+
+
 def _star(n_leaves, seed):
     """a centre atom bonded to n_leaves atoms (in-degree n_leaves at the centre, 1 at the leaves)"""
     rng = np.random.default_rng(seed)
